@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — frames/s of the Video K-Net kernel-update head on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: re-executes itself under torch.distributed.run, one rank per GPU;
+    python bench.py --gpus N --steps K --warmup W          (N > 1: runs itself under torch.distributed.run in a child process, one rank per GPU;
                                                             also runs when the driver already launched it that way)
 
 A "step" = one pass of the hot path over one clip of `--frames` synthetic 1024x2048 frames per GPU:
@@ -17,9 +17,14 @@ trains — samples_per_gpu = 1 — and infers, one frame per call): the SAME T-f
 `"scaling": "strong"`, value = T frames x steps / time.  At N = 1 the `breakdown` additionally carries the measured step time at
 T/2, T/4, ... 1 frames per call (per-rank compute on ONE GPU, labelled as such — not a scaling result).
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (mask-decode kernel, HIP-event timed, algorithmic bytes / time
-vs 8 TB/s HBM), "cpu_baseline" (the torch CPU oracle timed on this host, rank 0 / N=1 only), "breakdown" (incl. the whole step at
-1 / 8 / 32 frames per call: the reference walks a video one frame per call).
+Prints ONE JSON line (rank 0).  A plain run sets up, settles, warms up, times `--steps` steps and prints the line; everything
+else is measured only with `--full`, which adds the objects "roofline" (mask-decode kernel, HIP-event timed, algorithmic bytes /
+time vs 8 TB/s HBM), "cpu_baseline" (the torch CPU oracle timed on this host, rank 0 / N=1 only) and "breakdown" (incl. the whole
+step at 1 / 8 / 32 frames per call: the reference walks a video one frame per call).
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what its last timed step returned as DIR/<name>.npy (float32; an
+output larger than its share of 60 MB is written as a fixed, seeded sample of its flattened elements).  Weights and inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 `--train` (BASELINE cfg3, not the headline): one step = `forward_train_with_previous` of the same head on `--frames` frames per GPU
 (losses, Hungarian assignment, backward through the HIP kernels' autograd wrappers), bucketed RCCL all-reduce of the head's
@@ -46,6 +51,7 @@ def build_head(vkn, device, seed=0, link='ffn'):
     # link='update': the `*_joint_update` KITTI-STEP configs (previous_link='update_dynamic_cov', previous_type='update') — the
     # last stage of frame t depends on frame t-1's final kernels (bench.py --head update; never the headline line)
     over = dict(previous_link='update_dynamic_cov', previous_type='update') if link == 'update' else None
+    torch.manual_seed(seed)                  # the biases keep their construction-time init: seeded too, so every run has the same weights
     head = vkn.build_head(vkn.configs.roi_head_cfg(True, C=CFG2['C'], heads=CFG2['heads'], ffn=CFG2['ffn'], ncls=CFG2['ncls'],
                                n_thing=CFG2['n_thing'], n_stuff=CFG2['n_stuff'], S=CFG2['S'], up=CFG2['up'],
                                nprop=CFG2['nprop'], mask_over=over))
@@ -172,6 +178,30 @@ def _max_over_ranks(dt, steps, device, dist_on):
     return max(ts), [round(v / steps * 1e3, 4) for v in ts], dist.get_world_size()
 
 
+DUMP_BYTES = 60 << 20       # --dump-outputs writes at most this many bytes of float32 data in all
+
+
+def dump_outputs(out_dir, arrays, seed=2024):
+    """`--dump-outputs`: each tensor of `arrays` (name -> tensor) as out_dir/<name>.npy in float32.  A tensor with more elements than
+    its equal share of DUMP_BYTES is written as a sample: the elements at a fixed, seeded, sorted set of flat indices (the same set for
+    the same name and shape on every run)."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > cap:
+            g = torch.Generator(device='cpu').manual_seed(seed + zlib.crc32(name.encode()))
+            idx = torch.randint(0, flat.numel(), (cap,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+            a = flat.float().cpu().numpy()
+        else:
+            a = flat.float().cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def train_main(args, vkn, vkn_dist, device, world, rank, dist_on=False):
     """BASELINE cfg3: the clip's frames sharded over the ranks, head trained data-parallel (see the module docstring)."""
     B = args.frames if args.frames != 32 else 4            # frames per GPU per step (the inference default of 32 is not a training batch)
@@ -181,6 +211,7 @@ def train_main(args, vkn, vkn_dist, device, world, rank, dist_on=False):
     cfg = vkn.configs.roi_head_cfg(True, C=C, heads=CFG2['heads'], ffn=CFG2['ffn'], ncls=CFG2['ncls'], n_thing=CFG2['n_thing'],
                                    n_stuff=CFG2['n_stuff'], S=CFG2['S'], up=up, nprop=CFG2['nprop'],
                                    train_cfg=vkn.configs.rcnn_train_cfg(CFG2['S']))
+    torch.manual_seed(0)                                   # the construction-time init of the biases: identical on every rank and run
     head = vkn.build_head(cfg)
     torch.manual_seed(0)                                   # identical replicas
     head.init_weights()
@@ -235,12 +266,15 @@ def train_main(args, vkn, vkn_dist, device, world, rank, dist_on=False):
         with torch.cuda.stream(train_stream):
             return step_()
 
+    last_losses = {}
+
     def step_():
         reducer.zero_grad(set_to_none=not getattr(args, 'train_add_grads', False))
         if x.grad is not None:
             x.grad = None
         out = head.forward_train_with_previous(x, pf, mp, None, metas, gt_masks, gt_labels, gt_sem_seg=gt_sem_seg,
                                                gt_sem_cls=gt_sem_cls, previous_obj_feats=prev)
+        last_losses['losses'] = out[0]
         loss = sum(v for k, v in out[0].items() if 'loss' in k) + 1e-3 * (out[5] ** 2).mean()
         loss.backward()                                    # per-stage buckets are all-reduced (RCCL) as backward produces them
         reducer.finalize()
@@ -261,6 +295,12 @@ def train_main(args, vkn, vkn_dist, device, world, rank, dist_on=False):
     barrier()
     dt = time.perf_counter() - t0
     dt, per_rank_ms, ranks_seen = _max_over_ranks(dt, args.steps, device, dist_on)
+    if rank == 0 and args.dump_outputs:
+        # what the step hands its caller: the loss, the loss dictionary of forward_train_with_previous, the updated parameters
+        arrays = {'loss': loss.reshape(1)}
+        arrays.update({k: v.reshape(-1) for k, v in sorted(last_losses['losses'].items()) if torch.is_tensor(v)})
+        arrays['parameters'] = torch.cat([p.detach().reshape(-1) for p in head.parameters()])
+        dump_outputs(args.dump_outputs, arrays)
     if rank == 0:
         nparam = sum(p.numel() for p in head.parameters())
         print(json.dumps(dict(metric='training frames/sec (S=3, N=100, 1024x2048, head only)', value=round(world * B * args.steps / dt, 2),
@@ -299,9 +339,15 @@ def main():
                     help='STRONG scaling (BASELINE cfg3 shape): ONE clip of this many frames split into contiguous blocks of clip / N frames '
                          'per rank (clip 8 on 8 GPUs = one frame per GPU, as the reference trains and infers); overrides --frames.  '
                          'Default 0 = weak scaling at --frames per GPU')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: roofline (with the live decode-kernel events in the timed steps), '
+                         'breakdown (other batch sizes, kernels alone, x storage variants, the post-head pipeline) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, 60 MB at most: '
+                         'larger outputs as a fixed, seeded sample)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the extra data points of `breakdown` that launch other batch sizes / several clips (profiling runs)')
+                    help='--full: skip the extra data points of `breakdown` that launch other batch sizes / several clips (profiling runs)')
     ap.add_argument('--no-upsample', action='store_true', help='skip the x4 upsample output (diagnostic)')
     ap.add_argument('--train-up', type=int, default=4, choices=[1, 2, 4],
                     help='--train: mask_upsample_stride (4 = the shipped video KITTI-STEP config: 512x1024 loss masks; 2 = what rounds 2-5 timed)')
@@ -330,14 +376,17 @@ def main():
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if 'WORLD_SIZE' not in os.environ and (args.gpus > 1 or args.force_dist):
         # `python bench.py --gpus N` starts its own N ranks (the reference's launcher does the same from one command:
-        # tools/dist_train.sh:7-9): re-exec under torch.distributed.run, one process per GPU, rendezvous on 127.0.0.1
+        # tools/dist_train.sh:7-9): torch.distributed.run as a child process, one process per GPU, rendezvous on 127.0.0.1;
+        # this process touches no GPU and exits with the child's status
         import socket
+        import subprocess
         with socket.socket() as s_:
             s_.bind(('127.0.0.1', 0))
             port = s_.getsockname()[1]
         os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-        os.execv(sys.executable, [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={args.gpus}',
-                                  '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__), *sys.argv[1:]])
+        r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={args.gpus}',
+                            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__), *sys.argv[1:]])
+        raise SystemExit(r.returncode)
     if args.gpus != world:
         raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE={world}: launch as `python bench.py --gpus N` (self-launching) or with '
                          f'torch.distributed.run --nproc-per-node equal to --gpus')
@@ -430,6 +479,17 @@ def main():
         track = vkn.ops.track_link(dims, packs[-1], cur, prev)
         return outs, track
 
+    def step_outputs(res):
+        """What one step() hands its caller, by name: the five outputs of simple_test_mask_preds_plus_previous over this rank's frames
+        (without the x4 upsample, scaled_mask_preds is mask_preds)."""
+        outs, track = res
+        if not isinstance(outs, list):
+            outs = [outs]
+        names = ('object_feats', 'cls_score', 'mask_preds', 'scaled_mask_preds')
+        arrays = {n: torch.cat([o[k] for o in outs], 0) if len(outs) > 1 else outs[0][k] for k, n in enumerate(names)}
+        arrays['track'] = track
+        return arrays
+
     def barrier():
         if dist_on:
             dist.barrier()
@@ -462,25 +522,28 @@ def main():
                 break
         for _ in range(args.warmup):
             out = step()
-        # one HIP-event pair per timed step, recorded by the library around the LAST stage's mask-decode launch on the launch
-        # stream (vkn_head_forward_prof_f32): the roofline kernel is timed live, inside the timed region
-        dec_events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        # --full: one HIP-event pair per timed step, recorded by the library around the LAST stage's mask-decode launch on the
+        # launch stream (vkn_head_forward_prof_f32): the roofline kernel is timed live, inside the timed region
+        dec_events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                      for _ in range(args.steps if args.full else 0)]
         for e0_, e1_ in dec_events:      # the first record creates the underlying hipEvent_t
             e0_.record(streams[0])
             e1_.record(streams[0])
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            out = step(dec_events[i])
+            out = step(dec_events[i] if dec_events else None)
         barrier()
         dt = time.perf_counter() - t0
         dec_live_ms = sorted(e0_.elapsed_time(e1_) for e0_, e1_ in dec_events)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, step_outputs(out))
     dt, per_rank_ms, ranks_seen = _max_over_ranks(dt, args.steps, device, dist_on)
     frames = world * B * args.steps
     ms_per_step = dt / args.steps * 1e3
 
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         with torch.no_grad():
             # ---- roofline of the dominant x-streaming kernel with an HBM-bound design: k_decode_mfma (last stage), timed LIVE
             # inside the timed steps above (mean of the per-step HIP-event pairs); `isolated_*` = the same kernel in a

@@ -45,7 +45,7 @@ import knet.det.mask_pseudo_sampler  # noqa: E402,F401  (MaskPseudoSampler)
 import knet.cross_entropy_loss  # noqa: E402,F401  (the reference's own CrossEntropyLoss, registered with force=True)
 from mmdet.models.builder import NECKS, build_head  # noqa: E402
 
-OUT = os.environ.get('VKN_GOLDEN_OUT', os.path.join(ROOT, 'tests', 'golden'))   # tests/test_golden_regen.py regenerates into a tmp dir
+OUT = os.environ.get('VKN_GOLDEN_OUT', os.path.join(ROOT, 'tests', 'golden'))   # oracle/check_golden.py regenerates into a tmp dir
 
 
 def head_cfg(video, C, heads, ffn, ncls, n_thing, n_stuff, S, up, nprop, plink=None, ptype='ffn'):

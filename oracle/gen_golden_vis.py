@@ -43,7 +43,7 @@ import knet_vis.det.mask_pseudo_sampler  # noqa: E402,F401
 import knet.cross_entropy_loss  # noqa: E402,F401
 from mmdet.models.builder import build_head  # noqa: E402
 
-OUT = os.environ.get('VKN_GOLDEN_OUT', os.path.join(ROOT, 'tests', 'golden'))   # tests/test_golden_regen.py regenerates into a tmp dir
+OUT = os.environ.get('VKN_GOLDEN_OUT', os.path.join(ROOT, 'tests', 'golden'))   # oracle/check_golden.py regenerates into a tmp dir
 
 
 class AttrDict(dict):

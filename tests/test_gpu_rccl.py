@@ -173,9 +173,10 @@ def test_bench_previous_link_head_under_torchrun_one_rank():
 def test_bench_clip_of_8_strong_scaling_under_torchrun_one_rank():
     """`bench.py --clip 8` (BASELINE cfg3 shape: ONE clip of 8 frames in contiguous blocks of 8 / N per rank, strong scaling) launched
     the way the driver launches N-GPU runs — here one rank, RCCL initialised: the line says "strong", carries the whole clip on the one
-    rank, and the N = 1 breakdown holds the per-rank step times at 4 / 2 / 1 frames per call (what a rank of a 2 / 4 / 8-GPU run computes)."""
+    rank, and the N = 1 breakdown (--full) holds the per-rank step times at 4 / 2 / 1 frames per call (what a rank of a 2 / 4 / 8-GPU run
+    computes)."""
     port = _free_port()
-    line = _bench(['--force-dist', '--clip', '8'],
+    line = _bench(['--force-dist', '--clip', '8', '--full'],
                   launcher=['-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
                             '--master-port', str(port)])
     assert line['scaling'] == 'strong' and line['n_gpus'] == 1 and line['value'] > 0
@@ -187,7 +188,7 @@ def test_bench_clip_of_8_strong_scaling_under_torchrun_one_rank():
 
 
 def test_bench_self_launches_its_ranks_from_the_bare_command():
-    """`python bench.py --gpus 1 --force-dist` with no launcher and no WORLD_SIZE in the environment: bench.py re-executes itself
+    """`python bench.py --gpus 1 --force-dist` with no launcher and no WORLD_SIZE in the environment: bench.py runs itself
     under torch.distributed.run (the path `python bench.py --gpus 8` takes; reference: one command starts every rank,
     tools/dist_train.sh:7-9), RCCL is initialised, and the one JSON line reports the rank count the process group saw and every
     rank's own step time.  Also `--clip 8` and `--train` through the same path."""

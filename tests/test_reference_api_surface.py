@@ -1,75 +1,15 @@
 """Call signatures: for every class on the path that the reference defines and this package mirrors, every method the reference's
 class defines itself must exist here with the reference's parameter names in the reference's order (extra parameters here must
-have defaults) — what "same names, argument meaning" of a drop-in means mechanically.  The reference's classes are imported
-UNMODIFIED from /root/reference through the plumbing stand-ins of oracle/standins (as oracle/gen_golden.py does) in a child
-process; skipped where the reference tree is absent."""
+have defaults) — what "same names, argument meaning" of a drop-in means mechanically.  The reference's side is stored data
+(tests/golden/reference_api_surface.json: its classes imported UNMODIFIED through the plumbing stand-ins of oracle/standins by
+oracle/gen_golden_api.py, which also holds the list of class pairs)."""
 import inspect
 import json
 import os
-import subprocess
-import sys
 
-import pytest
+from oracle.gen_golden_api import PAIRS      # reference class -> class here
 
-REF = '/root/reference'
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='the reference tree is not present')
-
-# reference class -> (module, class here)
-PAIRS = {
-    'knet.kernel_updator:KernelUpdator': 'KernelUpdator',
-    'knet.det.kernel_update_head:KernelUpdateHead': 'KernelUpdateHead',
-    'knet.det.kernel_iter_head:KernelIterHead': 'KernelIterHead',
-    'knet.video.kernel_update_head:VideoKernelUpdateHead': 'VideoKernelUpdateHead',
-    'knet.video.kernel_iter_head:VideoKernelIterHead': 'VideoKernelIterHead',
-    'knet.det.kernel_head:ConvKernelHead': 'ConvKernelHead',
-    'knet.det.mask_hungarian_assigner:MaskHungarianAssigner': 'MaskHungarianAssigner',
-    'knet.det.mask_pseudo_sampler:MaskPseudoSampler': 'MaskPseudoSampler',
-    'knet_vis.tracker.kernel_head:ConvKernelHeadVideo': 'ConvKernelHeadVideo',
-    'knet_vis.tracker.kernel_update_head:KernelUpdateHeadVideo': 'KernelUpdateHeadVideo',
-    'knet_vis.tracker.kernel_iter_head:KernelIterHeadVideo': 'KernelIterHeadVideo',
-    'knet_vis.tracker.kernel_frame_iter_head:KernelFrameIterHeadVideo': 'KernelFrameIterHeadVideo',
-    'knet_vis.tracker.mask_hungarian_assigner:MaskHungarianAssignerVideo': 'MaskHungarianAssignerVideo',
-    'knet.video.qdtrack.trackers.quasi_dense_embed_tracker:QuasiDenseEmbedTracker': 'QuasiDenseEmbedTracker',
-    'knet.cross_entropy_loss:CrossEntropyLoss': 'losses.CrossEntropyLoss',
-    'knet.video.track_heads:QuasiDenseMaskEmbedHeadGTMask': 'QuasiDenseMaskEmbedHeadGTMask',
-}
-
-CHILD = r'''
-import sys, os, json, inspect, importlib
-sys.dont_write_bytecode = True
-root = sys.argv[1]
-sys.path.insert(0, os.path.join(root, 'oracle', 'standins'))
-sys.path.insert(1, '/root/reference')
-out = {}
-for key in sorted(json.loads(sys.argv[2]), key=lambda k: ('QuasiDenseEmbedTracker' in k) + 2 * ('QuasiDenseMaskEmbedHeadGTMask' in k)):
-    mod, cls = key.split(':')
-    try:
-        if cls == 'QuasiDenseEmbedTracker':      # its package __init__ needs cv2: loaded by path, as the golden generator does (last: it
-            sys.path.insert(0, root)             # replaces the `knet` package entries in sys.modules)
-            from oracle.gen_golden_tracker import load_reference_tracker
-            c = load_reference_tracker()
-        elif cls == 'QuasiDenseMaskEmbedHeadGTMask':   # knet/video/track_heads.py also holds RoI-based heads: loaded by path with name shims
-            sys.path.insert(0, root)
-            from oracle.gen_golden_tracker import load_reference_embed_head
-            c = load_reference_embed_head()
-        else:
-            c = getattr(importlib.import_module(mod), cls)
-    except Exception as e:            # a module the stand-ins cannot carry
-        out[key] = {'__error__': type(e).__name__ + ': ' + str(e)[:200]}
-        continue
-    ms = {}
-    for name, fn in vars(c).items():
-        if callable(fn) and (not name.startswith('_') or name in ('__init__', '_get_target_single', '_decode_init_proposals',
-                                                                 '_mask_forward', '_mask_forward_train')):
-            try:
-                ps = inspect.signature(fn).parameters.values()
-            except (TypeError, ValueError):
-                continue
-            ms[name] = [[p.name, p.default is not inspect._empty, p.kind.name] for p in ps]
-    out[key] = ms
-print('@@' + json.dumps(out))
-'''
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_api_surface.json')
 
 # methods of the reference this package deliberately does not carry (reason beside each)
 NOT_BUILT = {
@@ -81,10 +21,10 @@ NOT_BUILT = {
 
 
 def _reference_surface():
-    r = subprocess.run([sys.executable, '-c', CHILD, ROOT, json.dumps(sorted(PAIRS))], capture_output=True, text=True, timeout=600)
-    line = [l for l in r.stdout.splitlines() if l.startswith('@@')]
-    assert line, r.stderr[-2000:]
-    return json.loads(line[0][2:])
+    with open(FIXTURE) as f:
+        surf = json.load(f)
+    assert sorted(surf) == sorted(PAIRS), 'tests/golden/reference_api_surface.json does not cover the class pairs: run oracle/gen_golden_api.py'
+    return surf
 
 
 def test_methods_and_parameter_names_follow_the_reference(vkn):

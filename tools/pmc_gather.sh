@@ -9,7 +9,7 @@ for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" \
            "SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_VMEM SQ_INSTS_MFMA SQ_ACTIVE_INST_MISC SQ_WAIT_INST_VMEM" ; do
   i=$((i+1))
-  rocprofv3 --pmc $set -d $OUT/p$i -o p$i -- python $R/bench.py --steps 3 --warmup 1 --settle 2 --no-cpu-baseline > $OUT/p$i.log 2>&1
+  rocprofv3 --pmc $set -d $OUT/p$i -o p$i -- python $R/bench.py --full --steps 3 --warmup 1 --settle 2 --no-cpu-baseline > $OUT/p$i.log 2>&1
 done
 python - <<PY
 import sqlite3, glob
