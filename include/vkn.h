@@ -520,7 +520,10 @@ size_t vkn_panoptic_workspace_bytes(const VknPanopticCfg* cfg, int B, int N);
  *           nseg int32 [B] = number of segments (-1: internal capacity error, results invalid);
  *           bbox int32 [B][K][4] or NULL: (xmin, ymin, xmax, ymax) of `panoptic_seg == id` for accepted entries, else (-1,-1,10,10)
  *           = `tensor_mask2box` (unitrack/utils/mask.py:80-90) on the segment masks, what the video detector hands its tracker
- *           (knet/video/knet_quansi_dense_embed_fc_joint_train.py:541-584). */
+ *           (knet/video/knet_quansi_dense_embed_fc_joint_train.py:541-584).
+ *      Width limit: Wm <= 4096, else VKN_E_SHAPE.  The footprint-bounds pass keeps a strip of column (min, max) rows of the full
+ *      logit width in LDS; the strip is 8 tile rows high up to Wm = 512 and shrinks to 1 tile row at Wm = 4096.  (`get_panoptic`
+ *      passes up-scaled masks with up = 1: Wm = 624 for a KITTI-STEP frame, 1024 for a Cityscapes frame.) */
 int vkn_panoptic_joint_f32(const VknPanopticCfg* cfg, const float* cls_prob, const float* mask_logits, int B, int N, int ncls,
                            int* panoptic_seg, int* info, int* nseg, int* bbox, void* ws, size_t ws_bytes, void* stream);
 
@@ -685,7 +688,10 @@ int vkn_mask_losses_bwd_bank_f32(const float* pred, const float* bank, const int
 /* ... and WITHOUT the up-scaled gradient tensor (round 6): the predictions are the LOW-RES logits `low` [B][Ns][h][w]; the losses were taken on
  * their xS bilinear up-scaling (S = 2 or 4; F.interpolate(scale_factor=S, bilinear, align_corners=False), knet/det/kernel_iter_head.py:122-130)
  * against bank masks of [S h][S w]; grad_low [B][Ns][h][w] = d(sum of the weighted losses) / d low — the composition of
- * vkn_mask_losses_bwd_bank_f32 and vkn_upsample_bilinear_bwd_f32 in one pass (the [B Ns][S h][S w] gradient is never written). */
+ * vkn_mask_losses_bwd_bank_f32 and vkn_upsample_bilinear_bwd_f32 in one pass (the [B Ns][S h][S w] gradient is never written).
+ * The forward's limits: S = 2 or 4, Ns <= 256 (the rank target is held as one byte per pixel) and Ns h w * 4 < 2^31, else VKN_E_SHAPE;
+ * bank / lse / top 8-byte aligned, else VKN_E_ALIGN — both checked before anything is launched (the caller then takes the up-scaled
+ * gradient from vkn_mask_losses_bwd_bank_f32 and its adjoint from vkn_upsample_bilinear_bwd_f32). */
 int vkn_mask_losses_bwd_lowres_f32(const float* low, const float* bank, const int* tgt_row, const int* rowk, const float* dice_a,
                                    const float* dice_bc, const float* g_mask, const float* g_dice, const float* g_rank, float w_mask,
                                    float w_dice, float w_rank, int K, const float* lse, const int* top, int B, int Ns, int h, int w, int S,

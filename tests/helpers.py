@@ -97,6 +97,25 @@ def run_pan_oracle(case, b):
                               PAN_CFG['overlap_thr'], meta, upsample_stride=case['up'])
 
 
+def assert_pan_matches_oracle(seg, info, nseg, r, want_seg=None):
+    """One frame of the joint panoptic merge (seg [Ho, Wo], info [K, 6], nseg) against an oracle.panoptic_joint result `r`: selection
+    (rows / labels / score bits) and segment decisions exact; pixel counts and the map (`want_seg`, default the oracle's own) exact
+    except where the arg-max is decided by < 1e-6 (fp32 resampling noise)."""
+    assert int(nseg) == len(r['segments_info'])
+    assert np.array_equal(info[:, 0], r['rows'].numpy()) and np.array_equal(info[:, 1], r['total_labels'].numpy())
+    assert np.array_equal(info[:, 5].view(np.float32), r['total_scores'].numpy())       # score bits
+    assert np.array_equal(info[:, 2], r['seg_of'].numpy())                              # accept / reject + ids
+    near = (r['margin'].numpy() < 1e-6)
+    assert float(near.mean()) < 2e-3
+    n_near = int(near.sum())
+    assert np.abs(info[:, 3] - r['area'].numpy()).sum() <= 2 * n_near                   # pixels won
+    near_half = int(((r['total_masks'] - 0.5).abs() < 1e-6).sum())
+    assert np.abs(info[:, 4] - r['orig'].numpy()).sum() <= near_half                    # pixels with prob >= 0.5
+    diff = seg != (r['panoptic_seg'].numpy() if want_seg is None else want_seg)
+    assert not (diff & ~near).any()
+    assert int(diff.sum()) <= n_near
+
+
 def pan_info_rows(segments_info):
     """segments_info (list of dicts) -> the golden's [id, isthing, category_id, instance_id|-1, score|nan, area|-1] rows."""
     return np.array([[s['id'], int(s['isthing']), s['category_id'], s.get('instance_id', -1), s.get('score', float('nan')),
@@ -136,3 +155,42 @@ def record_margins(test_id, values):
     except OSError:
         pass
     print(f'[margins] {test_id}: ' + ', '.join(f'{k}={v:.3g}' if isinstance(v, float) else f'{k}={v}' for k, v in _MARGINS[test_id].items()))
+
+
+def lowres_tail_reference(low, bank, tgt_row, rowk, S, w=(1.0, 4.0, 0.1), g=(1.0, 1.0, 1.0), eps=1e-3):
+    """float64 reference of the loss tail on LOW-RES logits, autograd for the gradient (on low's device).  low [B, Ns, h, w]; bank
+    [G, S h, S w] target masks; rowk [B Ns] = positive index k of a row or -1; tgt_row [B Ns] = its bank row.  The reference's chain:
+    F.interpolate(scale_factor=S, bilinear, align_corners=False) (knet/det/kernel_iter_head.py:122-130), then `loss`
+    (knet/det/kernel_update_head.py:313-342) with mmdet's losses restated:
+      loss_mask = w[0] mean BCE-with-logits over the K positive rows (CrossEntropyLoss(use_sigmoid=True))
+      loss_dice = w[1] mean_k (1 - 2 a / (b + c)),  a = sum p t, b = sum p^2 + eps, c = sum t^2 + eps   (DiceLoss, sigmoid activated)
+      loss_rank = w[2] mean over B S h S w of the softmax CE over the Ns rows, target -1 ignored (CrossEntropyLoss(use_sigmoid=False),
+                  ignore_index=-1): the target of a pixel is the LAST positive row (in row order) whose mask covers it (:336-340).
+    -> dict(rows [K, 4] = per positive row (sum BCE, a, sum p^2, sum t^2), lse / top [B, P], rank_sum (sum of the CE), dice_a / dice_bc
+    [K] (what the backward kernels take), losses (3), grad [B, Ns, h, w] = d(sum_i g[i] loss_i) / d low)."""
+    import torch.nn.functional as F
+    B, Ns = low.shape[:2]
+    lo = low.detach().double().requires_grad_(True)
+    up = F.interpolate(lo, scale_factor=S, mode='bilinear', align_corners=False)
+    P = up.shape[2] * up.shape[3]
+    z = up.reshape(B, Ns, P)
+    rowk, tgt_row = rowk.long().to(low.device), tgt_row.long().to(low.device)
+    pos = torch.nonzero(rowk >= 0).flatten()
+    pos = pos[torch.argsort(rowk[pos])]                               # the row of positive k, k = 0 .. K-1
+    K = int(pos.numel())
+    tbank = bank.reshape(bank.shape[0], P).to(low.device)
+    pred = z.reshape(B * Ns, P)[pos]
+    tgt = tbank[tgt_row[pos]].double()
+    bce = F.binary_cross_entropy_with_logits(pred, tgt, reduction='none').sum(1)
+    p = pred.sigmoid()
+    a, b, c = (p * tgt).sum(1), (p * p).sum(1), (tgt * tgt).sum(1)
+    top = torch.full((B, P), -1, dtype=torch.long, device=low.device)
+    for r in sorted(pos.tolist()):                                    # positive rows in order: a later row overwrites an earlier one
+        top[r // Ns][tbank[tgt_row[r]] != 0] = r % Ns
+    ce = F.cross_entropy(z, top, ignore_index=-1, reduction='none')    # [B, P], 0 where ignored
+    losses = (bce.sum() / (K * P), (1 - 2 * a / ((b + eps) + (c + eps))).mean(), ce.sum() / (B * P))
+    total = sum(gi * wi * li for gi, wi, li in zip(g, w, losses))
+    total.backward()
+    return dict(rows=torch.stack([bce, a, b, c], 1).detach(), lse=torch.logsumexp(z, 1).detach(), top=top.int(),
+                rank_sum=float(ce.detach().sum()), dice_a=a.detach(), dice_bc=((b + eps) + (c + eps)).detach(),
+                losses=tuple(float(v.detach()) for v in losses), grad=lo.grad)

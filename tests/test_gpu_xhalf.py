@@ -25,7 +25,8 @@ def _clamp_tiny(x):
     return torch.where(x.abs() < 2.0 ** -13, s * 2.0 ** -13, x)
 
 
-CASES = [(2, 117, 256, 64, 128), (1, 100, 256, 48, 80), (3, 40, 64, 32, 64), (1, 216, 128, 32, 64)]
+CASES = [(2, 117, 256, 64, 128), (1, 100, 256, 48, 80), (3, 40, 64, 32, 64), (1, 216, 128, 32, 64),
+         (1, 117, 256, 48, 156)]   # KITTI-STEP frame: W = 156 is no multiple of 32, P = 7488 = 117 x 64
 
 
 @pytest.mark.parametrize('dt', [torch.float16, torch.bfloat16])
@@ -102,10 +103,13 @@ def test_half_x_head_matches_fp32_head_on_rounded_x_and_reference_within_toleran
 
 
 @pytest.mark.parametrize('golden,dt,tol,H,W,T', [('video_cfg', torch.bfloat16, 4e-2, 128, 256, 2),          # BASELINE cfg2 "bf16": 1024x2048, N = 117
-                                                 ('video_vipseg_big', torch.float16, 5e-3, 92, 160, 2)],   # BASELINE cfg5 "fp16": 720p, N = 166
-                         ids=['cfg2_bf16_128x256_N117', 'cfg5_fp16_92x160_N166'])
+                                                 ('video_vipseg_big', torch.float16, 5e-3, 92, 160, 2),    # BASELINE cfg5 "fp16": 720p, N = 166
+                                                 ('video_cfg', torch.float16, 5e-3, 48, 156, 2),           # KITTI-STEP frame (ragged width)
+                                                 ('video_cfg', torch.bfloat16, 4e-2, 48, 156, 2)],
+                         ids=['cfg2_bf16_128x256_N117', 'cfg5_fp16_92x160_N166', 'kitti_fp16_48x156_N117', 'kitti_bf16_48x156_N117'])
 def test_half_x_head_at_the_sizes_that_name_it(vkn, golden, dt, tol, H, W, T):
-    """The two BASELINE configs that WORD a half type, at their own feature size and kernel count: the whole fused head (3 stages,
+    """The two BASELINE configs that WORD a half type, at their own feature size and kernel count, and both half types at a KITTI-STEP
+    frame (48 x 156: a width that is no multiple of 32): the whole fused head (3 stages,
     clip link, x4 upsample) on half-storage x is bit-identical to the fp32 head on the rounded x (all three stage hand-offs), and
     the first stage's logits stay within the stated tolerance of the logit scale against the unrounded fp32 x."""
     from test_gpu_parity import _build_head

@@ -1327,7 +1327,9 @@ int vkn_mask_losses_bwd_lowres_f32(const float* low, const float* bank, const in
                                    int with_rank, float* grad_low, void* stream) {
     if (!low || !bank || !tgt_row || !rowk || !dice_a || !dice_bc || !grad_low || B <= 0 || Ns <= 0 || h <= 0 || w <= 0 || K <= 0) return VKN_E_ARG;
     if (with_rank && (!lse || !top)) return VKN_E_ARG;
-    if (S != 2 && S != 4) return VKN_E_SHAPE;
+    // the forward's limits: k_ml_bwd_lr holds the rank target `top` as one byte per pixel (row index < 256)
+    if ((S != 2 && S != 4) || Ns > 256 || (size_t)Ns * h * w * sizeof(float) >= (1ull << 31)) return VKN_E_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(bank) | reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(top)) & 7) return VKN_E_ALIGN;
     const double P = (double)S * h * (double)S * w;
     MlTail tl = {tgt_row, dice_a, dice_bc, g_mask, g_dice, g_rank, (float)((double)w_mask / ((double)K * P)),
                  (float)((double)w_dice / (double)K), (float)((double)w_rank / ((double)B * P))};

@@ -146,22 +146,25 @@ __device__ __forceinline__ void pan_region(const PanGeom& g, int X0, int tw, int
 // over the K selected planes (each row is read by the two or three tile rows whose footprints hold it: cache hits) instead of every
 // tile workgroup fetching the footprint of all K kernels (4.5x read over-fetch, eight dependent global round trips and a 55-element
 // serial min / max walk per kernel and tile: what made k_pan_argmax a 10 us-per-tile latency chain in round 5).
-// Workgroup = (PANB_KCH kernels) x (a strip of PANB_TR tile rows) x frame; thread = logit column: column-wise min / max over the tile
+// Workgroup = (PANB_KCH kernels) x (a strip of `tr` tile rows) x frame; thread = logit column: column-wise min / max over the tile
 // row's footprint rows -> LDS, then one (tile, kernel) pair per thread takes the min / max over the tile's footprint columns.
+// The strip keeps tr x PANB_KCH full-width rows of (min, max) pairs in LDS: tr = PANB_TR up to Wm = 512, fewer tile rows per strip
+// for wider maps (vkn_launch_panoptic_joint).  min / max do not depend on the order, so `bounds` is the same for every strip height.
 #define PANB_KCH 2
 #define PANB_TR 8
+#define PANB_LDS (64 * 1024)
 typedef float pan_f2 __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(256) void k_pan_bounds(PanGeom g, const float* __restrict__ masks, const int* __restrict__ sel_row, int K,
-                                                    int N, int ntx, int nty, pan_f2* __restrict__ bounds) {
+                                                    int N, int ntx, int nty, int tr, pan_f2* __restrict__ bounds) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    pan_f2* cmm = reinterpret_cast<pan_f2*>(smem);      // [PANB_TR tile rows][PANB_KCH][Wm] column (min, max) over the tile row's footprint rows
+    pan_f2* cmm = reinterpret_cast<pan_f2*>(smem);      // [tr tile rows][PANB_KCH][Wm] column (min, max) over the tile row's footprint rows
     const int tid = threadIdx.x, b = blockIdx.z, k0 = blockIdx.x * PANB_KCH, strip = blockIdx.y;
     const size_t plane = (size_t)g.Hm * g.Wm;
     const float* pl[PANB_KCH];
 #pragma unroll
     for (int kk = 0; kk < PANB_KCH; ++kk)
         pl[kk] = masks + ((size_t)b * N + sel_row[(size_t)b * K + min(k0 + kk, K - 1)]) * plane;
-    const int ty0 = strip * PANB_TR, ntr = min(nty - ty0, PANB_TR);
+    const int ty0 = strip * tr, ntr = min(nty - ty0, tr);
     // phase A: every tile row of the strip, no barrier in between; FOUR tile rows' loads (4 x 6 rows x PANB_KCH planes) are requested
     // before the first use — a wave that waits on 12 loads at a time was the whole cost of this kernel (5120 resident waves x 12 loads
     // per ~2 us round trip = 185 us for the 5.7 M wave-loads)
@@ -618,6 +621,10 @@ int vkn_launch_panoptic_joint(const VknPanopticCfg* c, const float* cls, const f
     if (c->up < 1 || c->Hm <= 0 || c->Wm <= 0 || c->Hb <= 0 || c->Wb <= 0 || c->h <= 0 || c->w <= 0 || c->Ho <= 0 || c->Wo <= 0)
         return VKN_E_ARG;
     if (c->h > c->Hb || c->w > c->Wb) return VKN_E_ARG;  // img_shape is a crop of batch_input_shape
+    // strip height of k_pan_bounds: PANB_TR tile rows up to Wm = 512 (64 KiB of column pairs), then as many as fit
+    const size_t row_bytes = (size_t)2 * PANB_KCH * c->Wm * 4;
+    const int tr = (int)(PANB_LDS / row_bytes < PANB_TR ? PANB_LDS / row_bytes : PANB_TR);
+    if (tr < 1) return VKN_E_SHAPE;   // Wm > 4096: one tile row's column pairs exceed the LDS of the pass
     if (ws_bytes < vkn_panoptic_ws_bytes(B, K, c->Ho, c->Wo)) return VKN_E_WORKSPACE;
     int* wsi = static_cast<int*>(ws);
     int* sel_row = wsi;
@@ -675,10 +682,9 @@ int vkn_launch_panoptic_joint(const VknPanopticCfg* c, const float* cls, const f
     KC = KC / PAN_KB * PAN_KB;
     lds += (size_t)KC * ln_bytes;
     dim3 grid((c->Wo + PAN_TW - 1) / PAN_TW, (c->Ho + PAN_TH - 1) / PAN_TH, B);
-    if ((size_t)2 * PANB_KCH * PANB_TR * g.Wm * 4 > 64 * 1024) return VKN_E_SHAPE;
     // (tried: an XCD-aware unit order that assembles every 128-byte line of `bounds` in one L2 — 168 us against 160: not the limit)
-    hipLaunchKernelGGL(k_pan_bounds, dim3((K + PANB_KCH - 1) / PANB_KCH, (grid.y + PANB_TR - 1) / PANB_TR, B), dim3(256),
-                       (size_t)2 * PANB_KCH * PANB_TR * g.Wm * 4, st, g, masks, sel_row, K, N, (int)grid.x, (int)grid.y, bounds);
+    hipLaunchKernelGGL(k_pan_bounds, dim3((K + PANB_KCH - 1) / PANB_KCH, (grid.y + tr - 1) / tr, B), dim3(256), (size_t)tr * row_bytes, st, g,
+                       masks, sel_row, K, N, (int)grid.x, (int)grid.y, tr, bounds);
     VKN_CHECK_LAUNCH();
     VKN_ALLOW_FULL_LDS(k_pan_argmax);
     hipLaunchKernelGGL(k_pan_argmax, grid, dim3(PAN_THREADS), lds, st, g, masks, sel_row, sel_score, K, N, panoptic_seg, area, orig, err,

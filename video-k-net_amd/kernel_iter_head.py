@@ -263,13 +263,15 @@ class KernelIterHead(BaseRoIHead):
         if self.fused_tail and self.x_hub and torch.is_grad_enabled() and torch.is_tensor(x) and x.is_cuda and x.requires_grad:
             from . import autograd as vag
             x = vag.x_hub(x)        # the six gradient contributions of x (a gather + a decode per stage) are summed in one pass
-        from .train_tail import TailStep
+        from .train_tail import TailStep, lowres_ok
         tail = TailStep.begin(self, x.device, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls)
         if tail is not None:
             gt_masks = tail.gt_views
         self._last_tail_fused = tail is not None     # (tests / bench: did the step's EVERY stage run the fused tail?)
-        # the low-res form of the tail's backward (no x`up` gradient tensor, no upsample adjoint): strides 2 / 4, plain fp32 CUDA logits
-        lowres = tail is not None and self.lowres_tail and up in (2, 4) and mask_preds.is_cuda and mask_preds.dtype == torch.float32
+        # the low-res form of the tail's backward (no x`up` gradient tensor, no upsample adjoint): plain fp32 CUDA logits within the
+        # low-res kernels' limits (strides 2 / 4, at most 256 rows per frame: train_tail.lowres_ok)
+        lowres = (tail is not None and self.lowres_tail and mask_preds.is_cuda and mask_preds.dtype == torch.float32
+                  and lowres_ok(mask_preds.shape, up))
         self._lowres_tail_step = bool(lowres)
         if self.mask_assigner and hasattr(self.mask_assigner[0], 'validate_labels'):
             # the labels do not change between stages: one range check for the whole step (on the device, reported asynchronously)

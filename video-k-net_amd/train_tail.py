@@ -66,6 +66,13 @@ def _shipped_losses(head):
                                 and lr.class_weight is None)))
 
 
+def lowres_ok(shape, stride):
+    """The limits of the low-res tail kernels (vkn_mask_losses_fwd_lowres_f32 / _bwd_lowres_f32, include/vkn.h) for low-res logits of
+    `shape` [B, Ns, h, w]: strides 2 / 4, at most 256 rows per frame (the rank target is held as one byte per pixel), Ns h w * 4 < 2^31."""
+    _, Ns, h, w = shape
+    return stride in (2, 4) and Ns <= 256 and Ns * h * w * 4 < 2 ** 31
+
+
 class TailStep:
     """The ground truth of one training step, laid out for the fused tail.  `begin` returns None whenever a precondition fails — the
     caller then runs the op-by-op path (same values)."""
@@ -182,10 +189,18 @@ class TailStep:
                                 float(head.loss_dice.eps), float(lr.loss_weight) if lr is not None else 0.0, t.avg_host,
                                 1 if lr is not None else 0)
         t.alpha, t.gamma = float(head.loss_cls.alpha), float(head.loss_cls.gamma)
-        if lowres is not None:
+        if lowres is not None and not (lowres_ok(lowres.shape, stride) and self.bank.data_ptr() % 8 == 0):
+            # beyond the low-res kernels' limits (vkn_mask_losses_bwd_lowres_f32: VKN_E_SHAPE): the losses on the up-scaled values,
+            # their gradient through the upsample's adjoint (ops.upsample_bilinear_bwd) into `lowres`
+            from .autograd import LazyUpsampleFn
+            if hasattr(scaled, 'materialize'):
+                scaled = scaled.materialize()
+            on = LazyUpsampleFn.apply(lowres, scaled.detach().contiguous(), int(stride))
+            l_cls, acc, l_mask, l_dice, l_rank = StageTailFn.apply(cls_score, on, t, None)
+        elif lowres is not None:
             t.stride = int(stride)
-            # forward sums from the low-res logits too (strides 2 / 4, up to 256 rows per frame); else from `scaled`
-            from_low = self.lowres_forward and stride in (2, 4) and Ns <= 256 and lowres.shape[1] * lowres.shape[2] * lowres.shape[3] * 4 < 2 ** 31
+            # forward sums from the low-res logits too; else (A/B arm) from `scaled`
+            from_low = self.lowres_forward
             if not from_low and hasattr(scaled, 'materialize'):
                 scaled = scaled.materialize()
             l_cls, acc, l_mask, l_dice, l_rank = StageTailFn.apply(cls_score, lowres, t, 'lowres' if from_low else scaled.detach())
