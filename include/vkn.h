@@ -772,6 +772,49 @@ int vkn_qd_tracker_match_f32(const VknTrackerCfg* cfg, void* state, size_t state
                              const float* embeds, int n, int frame_id, float* out_bboxes, int64_t* out_labels, int64_t* out_ids,
                              int* out_count, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- localization FPN of the kernel-initialisation head ("RPN"): `SemanticFPNWrapper` (knet/det/semantic_fpn_wrapper.py:33-237)
+ *      + the head's `loc_convs` / `seg_convs` (knet/det/kernel_head.py:150-159, 207-230).  Replaces `self.localization_fpn(img)`
+ *      and the loc / seg conv loops of `_decode_init_proposals` (:207-230): the whole upstream of vkn_kernel_init_f32.
+ *      Convs are implicit GEMMs on MFMA with the two-term f16 split (2^-22 relative operands, fp32 accumulation); GroupNorm (eps
+ *      1e-5, biased variance) and ReLU are applied by each conv's CONSUMER from fixed-order fp64-merged statistics (deterministic).
+ *      Activations must stay inside the f16-split envelope (|v| < 65504, finite): otherwise VKN_STATUS_RANGE is ORed into the
+ *      status word (the first four bytes of `ws`, vkn_workspace_status) and the outputs are garbage.
+ *
+ *      vkn_conv_prepare_f32: the weight of ONE conv, [Cout][Cin][k][k] fp32 (k = 1 or 3, Cout and Cin multiples of 32), into a
+ *      caller-owned image of vkn_conv_weight_bytes: f16 hi / lo MFMA fragments pre-scaled by a power of two (the power is stored in
+ *      the image and undone exactly by the consumer).  Regenerate whenever the weight changes. */
+size_t vkn_conv_weight_bytes(int Cout, int Cin, int ksize);
+int vkn_conv_prepare_f32(const float* w, int Cout, int Cin, int ksize, void* image, size_t image_bytes, void* stream);
+
+/* ---- building block: one mmcv `ConvModule(Cin, Cout, k, stride, padding=k//2, norm_cfg=GN(groups))` conv with its GroupNorm
+ *      statistics (knet/det/semantic_fpn_wrapper.py:83-146).  x [B][Cin][H][W] is the raw input (plus pos [Cin][H][W] if not
+ *      NULL, shared by the frames: the positional encoding of :203-212), or — in_stats != NULL — a previous conv's RAW output whose
+ *      GroupNorm (in_stats: (mean, rstd) per (frame, group) [B][in_groups][2], in_gamma / in_beta [Cin]) and ReLU are applied on
+ *      load, then with `upsample` the `nn.Upsample(scale_factor=2, mode='bilinear', align_corners=False)` of :117-121 on load (the
+ *      conv input is then 2H x 2W).  out [B][Cout][Ho][Wo] is the RAW conv output (Ho = ceil(Hin / stride)); out_stats [B][groups][2]
+ *      its (mean, rstd).  k = 3 (stride 1 or 2) or 1 (stride 1); Cin, Cout multiples of 32, <= 512.
+ *      ws: vkn_conv_gn_workspace_bytes, 256-byte status header first. */
+size_t vkn_conv_gn_workspace_bytes(int B, int Cout, int H, int W, int stride, int upsample);
+int vkn_conv_gn_f32(const float* x, const float* pos, const float* in_stats, const float* in_gamma, const float* in_beta, int in_groups,
+                    int upsample, const void* wimg, int ksize, int stride, int groups, float* out, float* out_stats, int B, int Cin,
+                    int H, int W, int Cout, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- the whole FPN of every shipped config (start_level 0, end_level 3, upsample_times 2, num_aux_convs 1, with_pred, GN + ReLU,
+ *      positional encoding at level 3, cat_coors / fuse_by_cat off), one stream, no host synchronisation or allocation.
+ *      p2..p5 [B][C][H_l][W_l]; every level must reach the stride-8 grid of P3: ceil(H2 / 2) = H3 = 2 H4 = 4 H5 (same for W),
+ *      else VKN_E_SHAPE.  pos5 [C][H5][W5] or NULL.  C a multiple of 32, <= 256; groups divides C.
+ *      wimg[10] (prepared images), gamma[10], beta[10] (GroupNorm affines), in this order: convs_all_levels.0.conv0,
+ *      .1.conv0, .2.conv0, .2.conv1, .3.conv0, .3.conv1, .3.conv2, conv_pred ‖ aux_convs.0 (ONE 2C-row 1x1 matrix and 2C-long
+ *      gamma / beta: the two convs read the same level sum), loc_convs.0, seg_convs.0.
+ *      wimg[8] == wimg[9] == NULL: loc / sem receive the module's own outputs [out, aux] (GN + ReLU'd); otherwise the outputs of
+ *      loc_convs.0(out) / seg_convs.0(aux) — exactly what vkn_kernel_init_f32 takes as loc_feats / sem_feats.  loc, sem [B][C][H3][W3].
+ *      ws: vkn_localization_fpn_workspace_bytes (pure host), 256-byte status header first. */
+size_t vkn_localization_fpn_workspace_bytes(int B, int C, int H2, int W2, int H3, int W3, int H4, int W4, int H5, int W5);
+int vkn_localization_fpn_f32(const float* p2, const float* p3, const float* p4, const float* p5, const float* pos5,
+                             const void* const* wimg, const float* const* gamma, const float* const* beta, int groups, float* loc,
+                             float* sem, int B, int C, int H2, int W2, int H3, int W3, int H4, int W4, int H5, int W5, void* ws,
+                             size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

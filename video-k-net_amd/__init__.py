@@ -1,7 +1,7 @@
 """video_k_net_amd — MI355X-native kernel-update head for Video K-Net (directory `video-k-net_amd/`).
 
 Importing this package registers `KernelUpdator` (TRANSFORMER_LAYER) and `KernelUpdateHead`, `VideoKernelUpdateHead`,
-`KernelIterHead`, `VideoKernelIterHead`, `ConvKernelHead` (HEADS) — into mmcv/mmdet's registries when they are importable, else into the bundled
+`KernelIterHead`, `VideoKernelIterHead`, `ConvKernelHead`, `SemanticFPNWrapper` (HEADS; mmdet's NECKS where that name is free) — into mmcv/mmdet's registries when they are importable, else into the bundled
 ones — so the reference's config dicts build these classes unchanged.  All arithmetic runs in
 `lib/libvkn.so` (hand-written HIP for gfx950, C ABI in include/vkn.h); there is no CPU fallback.
 """
@@ -10,6 +10,7 @@ from ._lib import VknError, VknLibraryError, build  # noqa: F401
 from .kernel_updator import KernelUpdator  # noqa: F401
 from .kernel_update_head import KernelUpdateHead, VideoKernelUpdateHead  # noqa: F401
 from .kernel_iter_head import KernelIterHead, VideoKernelIterHead  # noqa: F401
+from .semantic_fpn import SemanticFPNWrapper, SinePositionalEncoding  # noqa: F401
 from .kernel_head import ConvKernelHead, ConvKernelHeadVideo  # noqa: F401
 from .knet_vis import KernelFrameIterHeadVideo, KernelIterHeadVideo, KernelUpdateHeadVideo  # noqa: F401
 from .mask_hungarian_assigner import MaskHungarianAssigner, MaskHungarianAssignerVideo  # noqa: F401
@@ -21,6 +22,6 @@ from .mask_pseudo_sampler import MaskPseudoSampler  # noqa: F401
 
 registry._register_training_components()
 
-__all__ = ['KernelUpdator', 'KernelUpdateHead', 'VideoKernelUpdateHead', 'KernelIterHead', 'VideoKernelIterHead', 'ConvKernelHead', 'MaskHungarianAssigner', 'MaskHungarianAssignerVideo',
+__all__ = ['KernelUpdator', 'KernelUpdateHead', 'VideoKernelUpdateHead', 'KernelIterHead', 'VideoKernelIterHead', 'ConvKernelHead', 'SemanticFPNWrapper', 'MaskHungarianAssigner', 'MaskHungarianAssignerVideo',
            'HEADS', 'TRANSFORMER_LAYER', 'build_head', 'build_transformer_layer', 'ops', 'build', 'VknError',
            'VknLibraryError']

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libvkn.so')
-SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_api.hip')
+SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_api.hip')
 MAX_FCS = 4
 
 # every symbol include/vkn.h declares
@@ -32,7 +32,9 @@ SYMBOLS = ('vkn_version', 'vkn_strerror', 'vkn_workspace_init', 'vkn_workspace_s
            'vkn_mask_losses_bwd_bank_f32', 'vkn_mask_losses_bwd_lowres_f32', 'vkn_mask_losses_lowres_chunks', 'vkn_mask_losses_fwd_lowres_f32', 'vkn_scale_by_f32', 'vkn_sgd_momentum_f32', 'vkn_check_range_i64',
            'vkn_pow2_scale_f32', 'vkn_scale_pad_rows_f32', 'vkn_transpose_pad_f32', 'vkn_threshold_rows_f16', 'vkn_unscale_rows_f32', 'vkn_sum_n_f32',
            'vkn_sizeof_tracker_cfg', 'vkn_qd_tracker_state_bytes', 'vkn_qd_tracker_workspace_bytes', 'vkn_qd_tracker_state_layout',
-           'vkn_qd_tracker_reset', 'vkn_qd_tracker_match_f32')
+           'vkn_qd_tracker_reset', 'vkn_qd_tracker_match_f32',
+           'vkn_conv_weight_bytes', 'vkn_conv_prepare_f32', 'vkn_conv_gn_workspace_bytes', 'vkn_conv_gn_f32',
+           'vkn_localization_fpn_workspace_bytes', 'vkn_localization_fpn_f32')
 
 
 class VknPanopticCfg(ctypes.Structure):
@@ -373,6 +375,18 @@ def lib():
     L.vkn_query_merge_workspace_bytes.argtypes = [pD, c_int]
     L.vkn_query_merge_f32.restype = c_int
     L.vkn_query_merge_f32.argtypes = [pD, c_int, pW, _fp, _fp, _fp, _fp, _fp, c_size, _fp]
+    L.vkn_conv_weight_bytes.restype = c_size
+    L.vkn_conv_weight_bytes.argtypes = [c_int] * 3
+    L.vkn_conv_prepare_f32.restype = c_int
+    L.vkn_conv_prepare_f32.argtypes = [_fp, c_int, c_int, c_int, _fp, c_size, _fp]
+    L.vkn_conv_gn_workspace_bytes.restype = c_size
+    L.vkn_conv_gn_workspace_bytes.argtypes = [c_int] * 6
+    L.vkn_conv_gn_f32.restype = c_int
+    L.vkn_conv_gn_f32.argtypes = [_fp] * 5 + [c_int, c_int, _fp, c_int, c_int, c_int, _fp, _fp] + [c_int] * 5 + [_fp, c_size, _fp]
+    L.vkn_localization_fpn_workspace_bytes.restype = c_size
+    L.vkn_localization_fpn_workspace_bytes.argtypes = [c_int] * 10
+    L.vkn_localization_fpn_f32.restype = c_int
+    L.vkn_localization_fpn_f32.argtypes = [_fp] * 8 + [c_int, _fp, _fp] + [c_int] * 10 + [_fp, c_size, _fp]
     L.vkn_kernel_init_workspace_bytes.restype = c_size
     L.vkn_kernel_init_workspace_bytes.argtypes = [c_int] * 5
     L.vkn_kernel_init_f32.restype = c_int

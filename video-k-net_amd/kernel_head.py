@@ -5,9 +5,9 @@ knet/det/kernel_head.py:12-263, 506-515): same `HEADS` registration, ctor kwargs
 Scope: everything from the localization FPN's two feature maps to the first `KernelUpdateHead` —
 `init_kernels` / `conv_seg` 1x1 convs, `x_feats = semantic + loc`, the object-feature gather and the stuff-kernel concatenation —
 is ONE C-ABI call (`vkn_kernel_init_f32`: decode with frame-shared kernels + gather, the same HIP kernels as the head).
-The layers UPSTREAM of that (`localization_fpn`, the GroupNorm'ed `loc_convs` / `seg_convs` / `*_downsample`) belong to the backbone
-side, out of the hot-path scope: they are kept as ordinary torch modules so that checkpoints load and the class is usable
-end to end, and run on the GPU through PyTorch-ROCm.
+The layers UPSTREAM of that: with this package's `SemanticFPNWrapper` (semantic_fpn.py) of the shipped structure, one 1x1 GN conv in
+`loc_convs` and in `seg_convs` and no gradient needed, P2..P5 -> FPN -> loc / sem is ONE more C-ABI call (`vkn_localization_fpn_f32`);
+any other neck, the `*_downsample` convs and every call that needs a gradient run them as ordinary torch modules.
 """
 import torch
 import torch.nn as nn
@@ -17,6 +17,7 @@ from . import autograd as vag
 from . import ops
 from .losses import accuracy, reduce_mean
 from .registry import HAVE_MM, HEADS, build_assigner, build_loss, build_sampler, register_head
+from .semantic_fpn import SemanticFPNWrapper
 
 
 class _ConvGNReLU(nn.Module):
@@ -149,6 +150,9 @@ class ConvKernelHead(nn.Module):
         (knet/det/kernel_head.py:207-230)."""
         if self.localization_fpn is None:
             raise NotImplementedError('no localization_fpn was given: call decode_init_proposals_from_feats(loc, sem)')
+        fused = self._fused_upstream(img)
+        if fused is not None:
+            return fused
         feats = self.localization_fpn(img)
         loc = feats[0] if isinstance(feats, (list, tuple)) else feats
         for conv in self.loc_convs:
@@ -162,6 +166,22 @@ class ConvKernelHead(nn.Module):
                 sem = conv(sem)
             if self.feat_downsample_stride > 1 and self.feat_refine:
                 sem = self.seg_downsample(sem)
+        return loc, sem
+
+    def _fused_upstream(self, img):
+        """This package's `SemanticFPNWrapper` of the shipped structure, one 1x1 GN conv in `loc_convs` and in `seg_convs`, no
+        downsample and no gradient needed: the FPN and both convs are ONE C-ABI call (vkn_localization_fpn_f32).  None otherwise."""
+        fpn = self.localization_fpn
+        if not (isinstance(fpn, SemanticFPNWrapper) and fpn.fused_ok() and self.semantic_fpn and len(self.loc_convs) == 1
+                and len(self.seg_convs) == 1 and not (self.feat_downsample_stride > 1 and self.feat_refine)):
+            return None
+        convs = (self.loc_convs[0], self.seg_convs[0])
+        if any(c.conv.kernel_size != (1, 1) or c.conv.stride != (1, 1) or c.gn.num_groups != fpn.num_groups for c in convs):
+            return None
+        params = list(fpn.parameters()) + [p for c in convs for p in c.parameters()]
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in params) or any(x.requires_grad for x in img[:4])):
+            return None
+        loc, sem = fpn.forward_fused(img, *convs)
         return loc, sem
 
     def decode_init_proposals_from_feats(self, loc_feats, semantic_feats=None):

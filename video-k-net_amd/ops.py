@@ -1053,3 +1053,76 @@ def lsap(cost):
     if n < 0:
         check(n)
     return rows[:n].astype(np.int64), cols[:n].astype(np.int64)
+
+
+# ---------------------------------------------------------------------------------------------------------- localization FPN
+def conv_prepare(weight):
+    """One conv weight [Cout, Cin, k, k] -> its prepared image (uint8 tensor of vkn_conv_weight_bytes): f16 hi / lo MFMA fragments,
+    pre-scaled by a power of two (include/vkn.h: vkn_conv_prepare_f32).  Regenerate whenever the weight changes."""
+    w = _req(weight.detach(), 'conv weight')
+    Cout, Cin, kh, kw = w.shape
+    L = _lib.lib()
+    nb = L.vkn_conv_weight_bytes(Cout, Cin, kh) if kh == kw else 0
+    if not nb:
+        raise ValueError(f'conv weight {tuple(w.shape)}: needs k in (1, 3), Cout and Cin multiples of 32')
+    img = torch.empty(nb, dtype=torch.uint8, device=w.device)
+    with torch.cuda.device(w.device):
+        check(L.vkn_conv_prepare_f32(_ptr(w), Cout, Cin, kh, _ptr(img), nb, _stream()))
+    return img
+
+
+def conv_gn(x, image, Cout, ksize, stride=1, groups=32, pos=None, in_stats=None, in_gamma=None, in_beta=None, upsample=False):
+    """The building block (include/vkn.h: vkn_conv_gn_f32): a 3x3 (or 1x1) conv of `x` — raw (+ `pos`), or a previous conv's RAW
+    output GroupNorm'ed (in_stats [B, G_in, 2] = (mean, rstd), in_gamma / in_beta) and ReLU'd on load, optionally bilinear x2 on load —
+    returning (raw output [B, Cout, Ho, Wo], its (mean, rstd) per (frame, group) [B, groups, 2])."""
+    x = _req(x, 'x')
+    B, Cin, H, W = x.shape
+    Hin, Win = (2 * H, 2 * W) if upsample else (H, W)
+    Ho, Wo = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+    dev = x.device
+    out = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=dev)
+    st = torch.empty((B, groups, 2), dtype=torch.float32, device=dev)
+    ins = _req(in_stats, 'in_stats') if in_stats is not None else None
+    L = _lib.lib()
+    nb = L.vkn_conv_gn_workspace_bytes(B, Cout, H, W, stride, int(bool(upsample)))
+    if not nb:
+        raise ValueError('conv_gn: shape outside the envelope')
+    ws = _workspace(nb, dev)
+    with torch.cuda.device(dev):
+        check(L.vkn_conv_gn_f32(_ptr(x), _ptr(_req(pos, 'pos') if pos is not None else None), _ptr(ins),
+                                _ptr(_req(in_gamma, 'in_gamma') if ins is not None else None),
+                                _ptr(_req(in_beta, 'in_beta') if ins is not None else None), ins.shape[1] if ins is not None else 0,
+                                int(bool(upsample)), _ptr(image), int(ksize), int(stride), int(groups), _ptr(out), _ptr(st),
+                                B, Cin, H, W, int(Cout), _ptr(ws), ws.numel(), _stream()))
+    return out, st
+
+
+def localization_fpn(p2, p3, p4, p5, pos5, images, gammas, betas, groups):
+    """`SemanticFPNWrapper` of the shipped configs (+ the head's loc / seg convs when `images` has ten entries) in ONE C-ABI call
+    (include/vkn.h: vkn_localization_fpn_f32).  images / gammas / betas in the header's order; returns (loc, sem) [B, C, H3, W3]
+    — with eight images the module's own outputs (out, aux).  Range violations are reported through `workspace_status`."""
+    ps = [_req(p, f'P{i + 2}') for i, p in enumerate((p2, p3, p4, p5))]
+    B, C = ps[0].shape[:2]
+    if any(p.shape[:2] != (B, C) for p in ps):
+        raise ValueError('P2..P5 must share batch and channel counts')
+    dims = [int(d) for p in ps for d in p.shape[2:]]
+    dev = ps[0].device
+    L = _lib.lib()
+    nb = L.vkn_localization_fpn_workspace_bytes(B, C, *dims)
+    if not nb:
+        raise _lib.VknError(-2, 'localization_fpn: the levels do not reach one stride-8 grid (ceil(H2/2) = H3 = 2 H4 = 4 H5)')
+    H3, W3 = dims[2], dims[3]
+    loc = torch.empty((B, C, H3, W3), dtype=torch.float32, device=dev)
+    sem = torch.empty_like(loc)
+    n = len(images)
+    if n not in (8, 10):
+        raise ValueError('localization_fpn takes 8 or 10 prepared images')
+    arr = lambda ts: (ctypes.c_void_p * 10)(*[t.data_ptr() for t in ts], *([None] * (10 - len(ts))))  # noqa: E731
+    gs = [_req(g, 'gn.weight') for g in gammas]
+    bs = [_req(b, 'gn.bias') for b in betas]
+    pos = _req(pos5, 'pos') if pos5 is not None else None
+    ws = _workspace(nb, dev)
+    with torch.cuda.device(dev):
+        check(L.vkn_localization_fpn_f32(*[_ptr(p) for p in ps], _ptr(pos), arr(images), arr(gs), arr(bs), int(groups),
+                                         _ptr(loc), _ptr(sem), B, C, *dims, _ptr(ws), ws.numel(), _stream()))
+    return loc, sem
