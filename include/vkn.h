@@ -714,6 +714,43 @@ int vkn_sgd_momentum_f32(float* param, const float* grad, float* mom, size_t n, 
                          float grad_scale, void* stream);
 int vkn_check_range_i64(const long long* v, size_t n, long long lo, long long hi, int flag, int* status, void* stream);
 
+/* ---- AdamW behind a global L2 gradient clip over the flat gradient buckets: the optimizer of every shipped schedule
+ *      (configs/det/_base_/schedules/schedule_1x.py:1-8: AdamW lr 1e-4, weight_decay 0.05, grad_clip max_norm 1, norm_type 2),
+ *      built by external/train.py:67 (build_optimizer) and run by mmcv's OptimizerHook (external/train.py:98-104) as
+ *      clip_grad_norm_ + optimizer.step() every iteration.  One step of one device is three launches on `stream`, no host read:
+ *        k_adamw_sqnorm  sum of grad^2 per work item (fp64 accumulation, fixed order, one partial per item, no atomics);
+ *        k_adamw_finish  one workgroup: total_norm = sqrt(sum of the partials in fp64, fixed order); coef = clamp(max_norm /
+ *                        (float(total_norm) + 1e-6), max = 1) in fp32, NaN kept (torch.clamp); steps[i] += 1 where active[i];
+ *        k_adamw_update  one workgroup per work item: torch's single-tensor AdamW (decoupled weight decay) on g = grad * coef —
+ *                          p *= 1 - lr wd;  m = lerp(m, g, 1 - b1);  v = b2 v + (1 - b2) g^2;
+ *                          p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps),  bc1 = 1 - b1^step, bc2 = 1 - b2^step (fp64).
+ *      param, exp_avg, exp_avg_sq are updated in place; grad is only read (unlike clip_grad_norm_, which scales .grad in place, the
+ *      gradient keeps its unclipped value).  max_norm <= 0: no clip (the first launch is skipped, coef = 1, total_norm_out untouched).
+ *      items        DEVICE array of n_items work items: a chunk of one parameter (any count; the caller keeps it <= 16384 elements
+ *                   so that workgroups stay balanced).  n a multiple of 4, all four pointers 16-byte aligned: a zero-padded slot tail
+ *                   (dist.BucketedGradAllReducer) may be included and stays exactly zero.  Items with param_index / group_index out of
+ *                   range or a misaligned pointer are skipped by the kernels (never dereferenced).
+ *      group_rows   DEVICE double [n_groups][5]: lr, weight_decay, beta1, beta2, eps.
+ *      steps        DEVICE int [n_params], the per-parameter step counters; active: DEVICE uint8 [n_params], 0 = the parameter has no
+ *                   gradient this step (no decay, no moment update, no step increment, no part in the norm).
+ *      total_norm_out / coef_out  DEVICE float scalars or NULL.  ws: vkn_adamw_workspace_bytes (pure host), 16-byte aligned. */
+typedef struct VknAdamwItem {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int n;
+    int param_index;
+    int group_index;
+    int reserved;
+} VknAdamwItem;
+#define VKN_ADAMW_GROUP_ROW 5
+size_t vkn_sizeof_adamw_item(void);
+size_t vkn_adamw_workspace_bytes(int n_items, int n_params, int n_groups);
+int vkn_adamw_flat_f32(const VknAdamwItem* items, int n_items, int n_params, const double* group_rows, int n_groups, int* steps,
+                       const unsigned char* active, float max_norm, float* total_norm_out, float* coef_out, void* ws, size_t ws_bytes,
+                       void* stream);
+
 /* ---- glue of the BACKWARD passes of the two x-streaming ops (training; the passes themselves are vkn_mask_decode_scaled_f32 and
  *      vkn_mask_gather_real_f32 with transposed operands — knet/det/kernel_update_head.py:190-195, 247-260 differentiated):
  *        vkn_pow2_scale_f32      scale8[0] = the power of two s with max|t| s in [2^(target_log2 - 1), 2^target_log2) (s = 2^target_log2

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libvkn.so')
-SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_api.hip')
+SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_api.hip')
 MAX_FCS = 4
 
 # every symbol include/vkn.h declares
@@ -34,7 +34,8 @@ SYMBOLS = ('vkn_version', 'vkn_strerror', 'vkn_workspace_init', 'vkn_workspace_s
            'vkn_sizeof_tracker_cfg', 'vkn_qd_tracker_state_bytes', 'vkn_qd_tracker_workspace_bytes', 'vkn_qd_tracker_state_layout',
            'vkn_qd_tracker_reset', 'vkn_qd_tracker_match_f32',
            'vkn_conv_weight_bytes', 'vkn_conv_prepare_f32', 'vkn_conv_gn_workspace_bytes', 'vkn_conv_gn_f32',
-           'vkn_localization_fpn_workspace_bytes', 'vkn_localization_fpn_f32')
+           'vkn_localization_fpn_workspace_bytes', 'vkn_localization_fpn_f32',
+           'vkn_sizeof_adamw_item', 'vkn_adamw_workspace_bytes', 'vkn_adamw_flat_f32')
 
 
 class VknPanopticCfg(ctypes.Structure):
@@ -111,6 +112,14 @@ class VknDwItem(ctypes.Structure):
                 ('ldy', ctypes.c_int), ('lda', ctypes.c_int), ('Nout', ctypes.c_int), ('K', ctypes.c_int)]
 
 DW_MAX_ITEMS = 48
+
+
+class VknAdamwItem(ctypes.Structure):
+    """include/vkn.h: one work item of vkn_adamw_flat_f32 (a chunk of one parameter; device pointers as integers)"""
+    _fields_ = [('param', ctypes.c_void_p), ('grad', ctypes.c_void_p), ('exp_avg', ctypes.c_void_p), ('exp_avg_sq', ctypes.c_void_p),
+                ('n', ctypes.c_int), ('param_index', ctypes.c_int), ('group_index', ctypes.c_int), ('reserved', ctypes.c_int)]
+
+ADAMW_GROUP_ROW = 5     # VKN_ADAMW_GROUP_ROW: lr, weight_decay, beta1, beta2, eps (fp64)
 
 
 class VknUpdatorNorms(ctypes.Structure):
@@ -318,13 +327,14 @@ def lib():
     L.vkn_sizeof_dw_item.argtypes = []
     L.vkn_linear_dw_batch_f32.restype = c_int
     L.vkn_linear_dw_batch_f32.argtypes = [ctypes.POINTER(VknDwItem), c_int, c_int, _fp]
-    for fn in (L.vkn_sizeof_updator_norms, L.vkn_sizeof_updator_norm_grads):
+    for fn in (L.vkn_sizeof_updator_norms, L.vkn_sizeof_updator_norm_grads, L.vkn_sizeof_adamw_item):
         fn.restype = c_size
         fn.argtypes = []
     # the host-side item arrays / parameter blocks are handed to the kernels verbatim: a header edit without its mirror is garbage pointers
     for have, want, nm in ((L.vkn_sizeof_split_item(), ctypes.sizeof(VknSplitItem), 'VknSplitItem'), (L.vkn_sizeof_dw_item(), ctypes.sizeof(VknDwItem), 'VknDwItem'),
                            (L.vkn_sizeof_updator_norms(), ctypes.sizeof(VknUpdatorNorms), 'VknUpdatorNorms'),
-                           (L.vkn_sizeof_updator_norm_grads(), ctypes.sizeof(VknUpdatorNormGrads), 'VknUpdatorNormGrads')):
+                           (L.vkn_sizeof_updator_norm_grads(), ctypes.sizeof(VknUpdatorNormGrads), 'VknUpdatorNormGrads'),
+                           (L.vkn_sizeof_adamw_item(), ctypes.sizeof(VknAdamwItem), 'VknAdamwItem')):
         if have != want:
             raise VknLibraryError(f'ctypes mirror of include/vkn.h struct {nm} is out of date ({want} bytes here, {have} in the library)')
     L.vkn_linear_dw_f32.restype = c_int
@@ -448,6 +458,10 @@ def lib():
     L.vkn_scale_by_f32.argtypes = [_fp, _fp, _fp, ctypes.c_float, _fp, c_size, _fp]
     L.vkn_sgd_momentum_f32.restype = c_int
     L.vkn_sgd_momentum_f32.argtypes = [_fp, _fp, _fp, c_size] + [ctypes.c_float] * 4 + [_fp]
+    L.vkn_adamw_workspace_bytes.restype = c_size
+    L.vkn_adamw_workspace_bytes.argtypes = [c_int] * 3
+    L.vkn_adamw_flat_f32.restype = c_int
+    L.vkn_adamw_flat_f32.argtypes = [_fp, c_int, c_int, _fp, c_int, _fp, _fp, c_float, _fp, _fp, _fp, c_size, _fp]
     L.vkn_check_range_i64.restype = c_int
     L.vkn_check_range_i64.argtypes = [_fp, c_size, ctypes.c_longlong, ctypes.c_longlong, c_int, _fp, _fp]
     L.vkn_sum_n_f32.restype = c_int

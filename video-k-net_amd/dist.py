@@ -315,6 +315,26 @@ class BucketedGradAllReducer:
             b['fired'], b['nfired'], b['handle'], b['grew'] = {}, 0, None, False
 
 
+def _flatten_params(reducer, who):
+    """Move the parameters of every bucket of `reducer` into one flat fp32 buffer laid out like the bucket's gradient buffer (each
+    `p.data` becomes a view of it on the same 256-byte slot boundaries, values unchanged, padding zero) -> the flat buffers, in bucket
+    order.  The optimizers below run on the library's kernels only: anything but fp32 CUDA parameters raises (no CPU fallback)."""
+    for b in reducer.buckets:
+        if not b['flat'].is_cuda or b['flat'].dtype != torch.float32:
+            raise RuntimeError(f'{who} runs on the GPU kernels: fp32 CUDA parameters only (no CPU fallback)')
+    pflats = []
+    for b in reducer.buckets:
+        pflat = torch.zeros_like(b['flat'])
+        off = 0
+        for p in b['params']:
+            n = p.numel()
+            pflat[off:off + n].copy_(p.detach().reshape(-1))
+            p.data = pflat[off:off + n].view_as(p)
+            off += reducer._slot(n)
+        pflats.append(pflat)
+    return pflats
+
+
 class FlatSGD:
     """SGD with momentum over the FLAT buckets of a `BucketedGradAllReducer` (torch.optim.SGD's rule, dampening 0, no nesterov): the
     parameters of a bucket are moved into one flat buffer laid out like the bucket's gradient buffer (every `p.data` becomes a view of
@@ -329,20 +349,7 @@ class FlatSGD:
         if nesterov or dampening:
             raise NotImplementedError('FlatSGD: nesterov / dampening are not provided')
         self.reducer, self.lr, self.momentum, self.weight_decay = reducer, float(lr), float(momentum), float(weight_decay)
-        self.state = []
-        for b in reducer.buckets:
-            flat = b['flat']
-            if not flat.is_cuda or flat.dtype != torch.float32:
-                raise RuntimeError('FlatSGD runs on the GPU kernels: fp32 CUDA parameters only (no CPU fallback)')
-            pflat = torch.empty_like(flat)
-            pflat.zero_()
-            off = 0
-            for p in b['params']:
-                n = p.numel()
-                pflat[off:off + n].copy_(p.detach().reshape(-1))
-                p.data = pflat[off:off + n].view_as(p)
-                off += reducer._slot(n)
-            self.state.append(dict(param=pflat, mom=torch.zeros_like(flat)))
+        self.state = [dict(param=pflat, mom=torch.zeros_like(b['flat'])) for b, pflat in zip(reducer.buckets, _flatten_params(reducer, 'FlatSGD'))]
 
     def zero_grad(self, set_to_none=True):
         self.reducer.zero_grad(set_to_none=set_to_none)
@@ -361,3 +368,212 @@ class FlatSGD:
                                                   self.lr, self.momentum, self.weight_decay, 1.0,
                                                   torch.cuda.current_stream(b['flat'].device).cuda_stream))
 
+
+class FlatAdamW(torch.optim.Optimizer):
+    """AdamW behind a global L2 gradient clip over the FLAT buckets of a `BucketedGradAllReducer`: the optimizer of every shipped
+    schedule (configs/det/_base_/schedules/schedule_1x.py:1-8: AdamW lr 1e-4, weight_decay 0.05, grad_clip max_norm 1, norm_type 2),
+    which the reference runs as mmcv's OptimizerHook — `clip_grad_norm_(params, max_norm)` then `torch.optim.AdamW.step()` (external/
+    train.py:67, 98-104).  A step is ONE library call per device (`vkn_adamw_flat_f32`: squared-norm partials, a one-workgroup finish,
+    the update) over a work-item table built here once; it never reads anything back to the host.
+
+    * `params`: None (one group of every reducer parameter), an iterable of parameters, or torch-style group dicts (mmcv's
+      DefaultOptimizerConstructor makes one group per parameter).  Every listed parameter must belong to the reducer; reducer
+      parameters in no group are never touched.  torch.optim.lr_scheduler.* and mmcv's LR hooks drive `group['lr']` as usual.
+    * Layout: as FlatSGD, every reducer parameter becomes a view of one flat fp32 buffer per bucket (values unchanged), so the chain
+      kernels keep reading aligned views; exp_avg / exp_avg_sq live in two more flat buffers per bucket (`flat_state`).
+    * A parameter whose `.grad is None` after `reducer.finalize()` is skipped as torch.optim.AdamW skips it: no decay, no moment
+      update, no step, no part in the norm (its flat gradient slot may still hold an older step's values — only `.grad` decides).
+    * `max_norm` (None: no clip): the norm is taken over the parameters of this optimizer only.  After `step()`, `last_grad_norm` is
+      the fp32 device scalar `clip_grad_norm_` would have returned (what mmcv logs as `grad_norm`).  Unlike clip_grad_norm_, the flat
+      gradient is NOT scaled in place: after the step it still holds the reduced, unclipped gradient.
+    * `state_dict()` / `load_state_dict()` use torch.optim.AdamW's format (per parameter `step` as a 0-dim float32 tensor, `exp_avg`,
+      `exp_avg_sq`; torch's group keys), so checkpoints move between the two optimizers in both directions.  `state_dict()` reads the
+      step counters back to the host (checkpoint time, not every step).
+    Call order: `reducer.zero_grad -> backward -> reducer.finalize -> opt.step`.  fp32 parameters on ONE CUDA device; AMSGrad,
+    `maximize` and norms other than L2 are not provided (they raise)."""
+
+    CHUNK = 8192        # elements per work item (a workgroup of the norm and update kernels): one 16-byte load per lane and array, x8
+
+    def __init__(self, reducer, params=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=None, norm_type=2.0,
+                 amsgrad=False, *, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None):
+        if amsgrad or maximize or differentiable:
+            raise NotImplementedError('FlatAdamW: amsgrad / maximize / differentiable are not provided')
+        if float(norm_type) != 2.0:
+            raise NotImplementedError(f'FlatAdamW: only the L2 gradient norm is provided (norm_type={norm_type})')
+        if max_norm is not None and not float(max_norm) > 0:
+            raise ValueError(f'FlatAdamW: max_norm must be positive or None, got {max_norm}')
+        self._frozen = False
+        self.reducer = reducer
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.norm_type = 2.0
+        self.last_grad_norm = None
+        if params is None:
+            params = [p for b in reducer.buckets for p in b['params']]
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=foreach,
+                        capturable=capturable, differentiable=False, fused=fused, decoupled_weight_decay=True)
+        super().__init__(params, defaults)
+        where = {}
+        for bi, b in enumerate(reducer.buckets):
+            off = 0
+            for i, p in enumerate(b['params']):
+                where[id(p)] = (bi, i, off)
+                off += reducer._slot(p.numel())
+        for gi, g in enumerate(self.param_groups):
+            self._check_group(g)
+            for k, p in enumerate(g['params']):
+                if id(p) not in where:
+                    names = g.get('param_names')
+                    nm = f"'{names[k]}' " if names else ''
+                    raise ValueError(f"FlatAdamW: param_groups[{gi}]['params'][{k}] {nm}(shape {tuple(p.shape)}) is not a parameter of "
+                                     'the reducer')
+        self._params = [p for g in self.param_groups for p in g['params']]
+        used = sorted({where[id(p)][0] for p in self._params})
+        devs = {reducer.buckets[bi]['flat'].device for bi in used}
+        if len(devs) > 1:
+            raise NotImplementedError('FlatAdamW: the parameters span several devices (one process per GPU, as DDP)')
+        pflats = _flatten_params(reducer, 'FlatAdamW')
+        self.flat_state = [dict(param=pf, exp_avg=torch.zeros_like(pf), exp_avg_sq=torch.zeros_like(pf)) for pf in pflats]
+        dev = next(iter(devs))
+        self._device = dev
+        from . import _lib
+        items, self._mv, self._gviews = [], [], []
+        gi_of = [gi for gi, g in enumerate(self.param_groups) for _ in g['params']]
+        for pi, p in enumerate(self._params):
+            bi, i, off = where[id(p)]
+            b, st = reducer.buckets[bi], self.flat_state[bi]
+            n = p.numel()
+            self._mv.append((st['exp_avg'][off:off + n].view_as(p), st['exp_avg_sq'][off:off + n].view_as(p)))
+            self._gviews.append(b['views'][i])
+            n4 = (n + 3) // 4 * 4            # inside the 64-element slot: the zero padding stays exactly zero under AdamW
+            for c0 in range(0, n4, self.CHUNK):
+                o = 4 * (off + c0)
+                items.append(_lib.VknAdamwItem(st['param'].data_ptr() + o, b['flat'].data_ptr() + o, st['exp_avg'].data_ptr() + o,
+                                               st['exp_avg_sq'].data_ptr() + o, min(self.CHUNK, n4 - c0), pi, gi_of[pi], 0))
+        arr = (_lib.VknAdamwItem * len(items))(*items)
+        self._items = torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(dev)
+        self._n_items = len(items)
+        self._steps = torch.zeros(len(self._params), dtype=torch.int32, device=dev)
+        # group rows (fp64 [n_groups][5]) and active bytes ([n_params]) in ONE device buffer, rewritten from pinned memory on change
+        self._rows_bytes = 8 * _lib.ADAMW_GROUP_ROW * len(self.param_groups)
+        self._hyper = torch.zeros(self._rows_bytes + len(self._params), dtype=torch.uint8, device=dev)
+        self._staging = []              # [pinned buffer, event of its last copy]: a buffer is refilled only once its copy is done
+        self._uploaded = None
+        nb = _lib.lib().vkn_adamw_workspace_bytes(self._n_items, len(self._params), len(self.param_groups))
+        self._ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
+        self._frozen = True
+
+    @staticmethod
+    def _check_group(g):
+        if g.get('amsgrad') or g.get('maximize') or g.get('differentiable'):
+            raise NotImplementedError('FlatAdamW: amsgrad / maximize / differentiable are not provided')
+        b1, b2 = g['betas']
+        if not (0.0 <= float(g['lr']) and 0.0 <= float(g['eps']) and 0.0 <= float(g['weight_decay']) and 0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"FlatAdamW: invalid hyper-parameters lr={g['lr']} betas={g['betas']} eps={g['eps']} "
+                             f"weight_decay={g['weight_decay']}")
+
+    def add_param_group(self, param_group):
+        if self._frozen:
+            raise NotImplementedError('FlatAdamW: the parameter groups are fixed at construction (the work-item table is built once)')
+        super().add_param_group(param_group)
+
+    def zero_grad(self, set_to_none=True):
+        self.reducer.zero_grad(set_to_none=set_to_none)
+
+    def _active(self):
+        act = []
+        for p, v in zip(self._params, self._gviews):
+            g = p.grad
+            if g is not None and g is not v and g.data_ptr() != v.data_ptr():
+                raise RuntimeError('FlatAdamW: a gradient is not in its bucket — call reducer.finalize() before step()')
+            act.append(g is not None)
+        return act
+
+    def _upload(self, stream):
+        """Group rows + active bytes to the device when they changed: a non-blocking copy from a pinned buffer that no copy in flight
+        still reads (an event per buffer; a new buffer when every one is busy) — no host synchronisation."""
+        import numpy as np
+        rows = [(float(g['lr']), float(g['weight_decay']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps'])) for g in self.param_groups]
+        act = self._active()
+        key = (rows, act)
+        if key == self._uploaded:
+            return
+        slot = next((s for s in self._staging if s[1].query()), None)
+        if slot is None:
+            slot = [torch.empty(self._hyper.numel(), dtype=torch.uint8, pin_memory=True), torch.cuda.Event()]
+            self._staging.append(slot)
+        h = slot[0].numpy()
+        h[:self._rows_bytes] = np.asarray(rows, dtype=np.float64).reshape(-1).view(np.uint8)
+        h[self._rows_bytes:] = np.asarray(act, dtype=np.uint8)
+        self._hyper.copy_(slot[0], non_blocking=True)
+        slot[1].record(stream)
+        self._uploaded = key
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        from . import _lib
+        L = _lib.lib()
+        dev = self._device
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            self._upload(stream)
+            norm = torch.empty((), dtype=torch.float32, device=dev) if self.max_norm is not None else None
+            _lib.check(L.vkn_adamw_flat_f32(self._items.data_ptr(), self._n_items, len(self._params), self._hyper.data_ptr(),
+                                            len(self.param_groups), self._steps.data_ptr(), self._hyper.data_ptr() + self._rows_bytes,
+                                            self.max_norm or 0.0, None if norm is None else norm.data_ptr(), None,
+                                            self._ws.data_ptr(), self._ws.numel(), stream.cuda_stream))
+        self.last_grad_norm = norm
+        return loss
+
+    def state_dict(self):
+        steps = self._steps.cpu().tolist()
+        state = {}
+        for i, (m, v) in enumerate(self._mv):
+            if steps[i] > 0:            # a parameter that never had a gradient has no state (as in torch)
+                state[i] = {'step': torch.tensor(float(steps[i]), dtype=torch.float32), 'exp_avg': m.clone(), 'exp_avg_sq': v.clone()}
+        groups, start = [], 0
+        for g in self.param_groups:
+            d = {k: v for k, v in g.items() if k != 'params'}
+            d['params'] = list(range(start, start + len(g['params'])))
+            start += len(g['params'])
+            groups.append(d)
+        return {'state': state, 'param_groups': groups}
+
+    def load_state_dict(self, state_dict):
+        saved = state_dict['param_groups']
+        if len(saved) != len(self.param_groups) or any(len(s['params']) != len(g['params']) for s, g in zip(saved, self.param_groups)):
+            raise ValueError('FlatAdamW.load_state_dict: the saved parameter groups do not match this optimizer\'s')
+        index = {}
+        for s, g, start in zip(saved, self.param_groups, _prefix_sums([len(g['params']) for g in self.param_groups])):
+            self._check_group(dict(s, params=None))
+            for k, saved_id in enumerate(s['params']):
+                index[saved_id] = start + k
+        steps = torch.zeros(len(self._params), dtype=torch.int32)
+        with torch.no_grad():
+            for st in self.flat_state:
+                st['exp_avg'].zero_()
+                st['exp_avg_sq'].zero_()
+            for saved_id, st in state_dict['state'].items():
+                i = index[saved_id]
+                m, v = self._mv[i]
+                m.copy_(st['exp_avg'])
+                v.copy_(st['exp_avg_sq'])
+                steps[i] = int(round(float(st['step'])))
+            self._steps.copy_(steps)
+        for s, g in zip(saved, self.param_groups):
+            ps = g['params']
+            g.clear()
+            g.update({k: v for k, v in s.items() if k != 'params'})
+            g['params'] = ps
+        self._uploaded = None
+
+
+def _prefix_sums(lens):
+    out, s = [], 0
+    for n in lens:
+        out.append(s)
+        s += n
+    return out
