@@ -393,7 +393,7 @@ def test_chain_graph_gradient_delivery_survives_inplace_zero_and_accumulation(vk
 
 
 def test_python_flag_constants_match_the_header(vkn):
-    """`ops.FLAG_*` / `ops.PHASE_*` are typed by hand: they must equal include/vkn.h's VKN_FLAG_* values (and no two flags may share a bit)."""
+    """`ops.FLAG_*` / `ops.PHASE_*` are read from include/vkn.h: the names callers use must exist and equal the VKN_FLAG_* values (and no two flags may share a bit)."""
     import re
     text = open(os.path.join(ROOT, 'include', 'vkn.h')).read()
     hdr = {m.group(1): int(m.group(2)) for m in re.finditer(r'#define VKN_FLAG_(\w+) (\d+)u', text)}
@@ -444,6 +444,82 @@ def test_public_header_is_plain_c(tmp_path):
                    '  (void)d; (void)w; (void)a; (void)b; (void)c; (void)g; return vkn_version() == 0; }\n')
     r = subprocess.run([gcc, '-std=c99', '-Wall', '-Wextra', '-Werror', '-fsyntax-only', '-I', root, str(src)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+
+
+def test_struct_mirrors_have_the_layout_a_c_compiler_gives_the_header(vkn, tmp_path):
+    """The ctypes mirrors are computed from include/vkn.h by `_lib.read_header`; a C compiler, not that reader, is the judge of the result:
+    offset and size of every field and the size of every struct, as `_Static_assert`s in a translation unit that includes the header
+    (C11 for `_Static_assert` — this generated file only).  Catches what the library's `vkn_sizeof_*` probes cannot: two fields of one
+    size swapped, a float read as an int."""
+    import shutil
+    import subprocess
+    gcc = shutil.which('gcc')
+    if gcc is None:
+        pytest.skip('no gcc in this environment')
+    mirrors = vkn._lib.MIRRORS
+    assert len(mirrors) == 14 and all(getattr(vkn._lib, n) is m for n, m in mirrors.items())
+    lines = ['#include <stddef.h>', '#include "include/vkn.h"']
+    for name, m in mirrors.items():
+        lines.append(f'_Static_assert(sizeof({name}) == {ctypes.sizeof(m)}, "sizeof {name}");')
+        for field, _ in m._fields_:
+            f = getattr(m, field)
+            lines.append(f'_Static_assert(offsetof({name}, {field}) == {f.offset}, "offsetof {name}.{field}");')
+            lines.append(f'_Static_assert(sizeof((({name}*)0)->{field}) == {f.size}, "sizeof {name}.{field}");')
+    assert len(lines) > 2 + 14 + 2 * 150
+    src = tmp_path / 'layout.c'
+    src.write_text('\n'.join(lines) + '\n')
+    r = subprocess.run([gcc, '-std=c11', '-Wall', '-Wextra', '-Werror', '-fsyntax-only', '-I', ROOT, str(src)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_prototypes_are_the_headers(vkn):
+    """`lib()` sets restype / argtypes of every entry point from include/vkn.h.  Pinned here, written out: one entry point per type class
+    (struct pointers, doubles, long long, the device-memory struct array, pointer-to-pointer, a string result); and for every declared
+    function the argument count this test's own reading of the header gives."""
+    L = vkn._lib.lib()
+    c_int, c_uint, c_size, c_float, c_double, c_ll, p = (ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.c_float, ctypes.c_double,
+                                                         ctypes.c_longlong, ctypes.c_void_p)
+    pD, pW = ctypes.POINTER(vkn._lib.VknDims), ctypes.POINTER(vkn._lib.VknStageWeights)
+    pins = {
+        'vkn_head_forward_f32': (c_int, [pD, c_int, pW, p, p, p, p, p, p, p, p, c_int, p, p, c_size, c_uint, p]),
+        'vkn_panoptic_thing_first_u8': (c_int, [p, p, p, p, c_int, p, p, p, c_int, c_int, c_double, c_double, c_int, p, p, p, p, c_size, p]),
+        'vkn_check_range_i64': (c_int, [p, c_size, c_ll, c_ll, c_int, p, p]),
+        'vkn_adamw_flat_f32': (c_int, [p, c_int, c_int, p, c_int, p, p, c_float, p, p, p, c_size, p]),     # items: DEVICE memory, not POINTER(VknAdamwItem)
+        'vkn_sum_n_f32': (c_int, [ctypes.POINTER(ctypes.c_void_p), c_int, c_size, p, p]),
+        'vkn_strerror': (ctypes.c_char_p, [c_int]),
+        'vkn_sizeof_dims': (c_size, []),
+    }
+    for name, (restype, argtypes) in pins.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype, (name, fn.restype)
+        assert list(fn.argtypes) == argtypes, (name, fn.argtypes)
+    text = re.sub(r'/\*.*?\*/', ' ', open(os.path.join(ROOT, 'include', 'vkn.h')).read(), flags=re.S)
+    declared = re.findall(r'\b(vkn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', text)
+    assert len(declared) == len(vkn._lib.SYMBOLS) == 111
+    for name, params in declared:
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and fn.restype in (c_int, c_size, ctypes.c_char_p), name
+        assert len(fn.argtypes) == (0 if params.strip() == 'void' else params.count(',') + 1), name
+
+
+def test_header_reader_refuses_what_it_does_not_know(vkn):
+    """`_lib.read_header` handles the C subset include/vkn.h is written in and nothing else: an unknown type or a function-pointer
+    parameter is an error naming the declaration, never a guessed `void*`."""
+    read = vkn._lib.read_header
+    protos, structs, consts = read('#define VKN_A 2u\n#define VKN_B (-3)\n#define VKN_C 0x10\n#define VKN_D (VKN_A | VKN_C)\n'
+                                   'typedef struct VknT { const float *a, *b[VKN_A]; int n; } VknT;\n'
+                                   'int vkn_ok(const VknT* t, const float* const* rows, size_t n, void* stream);\nsize_t vkn_none(void);\n')
+    assert consts == dict(VKN_A=2, VKN_B=-3, VKN_C=16, VKN_D=18)
+    assert structs == dict(VknT=[('a', 'float', 1, None), ('b', 'float', 1, 2), ('n', 'int', 0, None)])
+    assert protos == dict(vkn_ok=(('int', 0), [('t', 'VknT', 1), ('rows', 'float', 2), ('n', 'size_t', 0), ('stream', 'void', 1)]),
+                          vkn_none=(('size_t', 0), []))
+    for bad, named in (('int vkn_odd(const float* x, half_t scale, void* stream);', 'vkn_odd'),
+                       ('int vkn_callback(void (*done)(int), void* stream);', 'vkn_callback'),
+                       ('typedef struct VknU { wchar_t* s; } VknU;', 'VknU'),
+                       ('#define VKN_E (1 << 4)', 'VKN_E')):
+        with pytest.raises(vkn.VknLibraryError) as e:
+            read(bad)
+        assert named in str(e.value), (bad, str(e.value))
 
 
 def test_device_assign_result_is_lazy_and_equal_to_the_eager_fields(vkn):

@@ -1,10 +1,11 @@
-"""ctypes binding of libvkn.so (C ABI in include/vkn.h) + the hipcc build recipe.
+"""ctypes binding of libvkn.so, computed from its C ABI in include/vkn.h, + the hipcc build recipe.
 
 The library is built IN-TREE (`video-k-net_amd/lib/libvkn.so`) so that it travels with the repo snapshot to the GPU
 box; there is no CPU fallback: if the library is missing every op raises `VknLibraryError`.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -12,77 +13,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libvkn.so')
 SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_api.hip')
-MAX_FCS = 4
-
-# every symbol include/vkn.h declares
-SYMBOLS = ('vkn_version', 'vkn_strerror', 'vkn_workspace_init', 'vkn_workspace_status', 'vkn_sizeof_dims', 'vkn_sizeof_stage_weights', 'vkn_gather_workspace_bytes', 'vkn_mask_gather_f32', 'vkn_mask_gather_real_f32',
-           'vkn_decode_workspace_bytes', 'vkn_mask_decode_f32', 'vkn_mask_decode_scaled_f32', 'vkn_split_planes_f32', 'vkn_mask_decode_planes_f32',
-           'vkn_decode_gather_supported', 'vkn_decode_gather_f32', 'vkn_mask_decode_planes_x', 'vkn_decode_gather_x',
-           'vkn_track_link_f32', 'vkn_track_link_flags_f32', 'vkn_prepared_bytes', 'vkn_prepare_stage_f32', 'vkn_split_weight_f32', 'vkn_linear_f32', 'vkn_split_weight_t_f32', 'vkn_sizeof_split_item', 'vkn_split_weights_batch_f32', 'vkn_linear_dw_f32', 'vkn_sizeof_dw_item', 'vkn_sizeof_updator_norms', 'vkn_sizeof_updator_norm_grads', 'vkn_linear_dw_batch_f32', 'vkn_layernorm_act_fwd_f32', 'vkn_layernorm_act_bwd_f32', 'vkn_updator_gate_product_f32', 'vkn_updator_gate_product_bwd_f32', 'vkn_updator_mix_fwd_f32', 'vkn_updator_mix_bwd_f32', 'vkn_attention_f32', 'vkn_attention_bwd_f32', 'vkn_upsample_bilinear_f32', 'vkn_upsample_bilinear_f16out', 'vkn_upsample_bilinear_bwd_f32', 'vkn_kernel_updator_f32',
-           'vkn_stage_workspace_bytes', 'vkn_stage_forward_f32', 'vkn_stage_chain_f32', 'vkn_head_workspace_bytes', 'vkn_head_forward_f32', 'vkn_focal_loss_blocks', 'vkn_focal_loss_f32',
-           'vkn_head_forward_prof_f32', 'vkn_head_forward_link_f32', 'vkn_stage_forward_link_f32', 'vkn_link_block_f32',
-           'vkn_query_merge_workspace_bytes', 'vkn_query_merge_f32',
-           'vkn_kernel_init_workspace_bytes', 'vkn_kernel_init_f32',
-           'vkn_sizeof_panoptic_cfg', 'vkn_panoptic_workspace_bytes', 'vkn_panoptic_joint_f32',
-           'vkn_merge_workspace_bytes', 'vkn_panoptic_thing_first_u8',
-           'vkn_sizeof_assign_cfg', 'vkn_assign_workspace_bytes', 'vkn_assign_costs_f32', 'vkn_sizeof_assign_problem', 'vkn_assign_costs_batch_f32', 'vkn_assign_lowres_workspace_bytes', 'vkn_assign_costs_lowres_batch_f32', 'vkn_lsap_f32',
-           'vkn_sizeof_lsap_problem', 'vkn_lsap_batch_f32',
-           'vkn_mask_losses_chunks', 'vkn_mask_losses_blocks', 'vkn_mask_losses_fwd_f32', 'vkn_mask_losses_bwd_f32',
-           'vkn_sizeof_tail_image', 'vkn_sizeof_tail_cfg', 'vkn_stage_targets', 'vkn_mask_losses_fwd_bank_f32', 'vkn_stage_losses_final_f32',
-           'vkn_mask_losses_bwd_bank_f32', 'vkn_mask_losses_bwd_lowres_f32', 'vkn_mask_losses_lowres_chunks', 'vkn_mask_losses_fwd_lowres_f32', 'vkn_scale_by_f32', 'vkn_sgd_momentum_f32', 'vkn_check_range_i64',
-           'vkn_pow2_scale_f32', 'vkn_scale_pad_rows_f32', 'vkn_transpose_pad_f32', 'vkn_threshold_rows_f16', 'vkn_unscale_rows_f32', 'vkn_sum_n_f32',
-           'vkn_sizeof_tracker_cfg', 'vkn_qd_tracker_state_bytes', 'vkn_qd_tracker_workspace_bytes', 'vkn_qd_tracker_state_layout',
-           'vkn_qd_tracker_reset', 'vkn_qd_tracker_match_f32',
-           'vkn_conv_weight_bytes', 'vkn_conv_prepare_f32', 'vkn_conv_gn_workspace_bytes', 'vkn_conv_gn_f32',
-           'vkn_localization_fpn_workspace_bytes', 'vkn_localization_fpn_f32',
-           'vkn_sizeof_adamw_item', 'vkn_adamw_workspace_bytes', 'vkn_adamw_flat_f32')
-
-
-class VknPanopticCfg(ctypes.Structure):
-    """Mirror of include/vkn.h: VknPanopticCfg."""
-    _fields_ = [('num_proposals', ctypes.c_int), ('num_thing_classes', ctypes.c_int), ('max_per_img', ctypes.c_int),
-                ('instance_score_thr', ctypes.c_float), ('overlap_thr', ctypes.c_double), ('up', ctypes.c_int),
-                ('Hm', ctypes.c_int), ('Wm', ctypes.c_int), ('Hb', ctypes.c_int), ('Wb', ctypes.c_int),
-                ('h', ctypes.c_int), ('w', ctypes.c_int), ('Ho', ctypes.c_int), ('Wo', ctypes.c_int)]
-
-
-class VknAssignCfg(ctypes.Structure):
-    """Mirror of include/vkn.h: VknAssignCfg."""
-    _fields_ = [('cls_weight', ctypes.c_float), ('dice_weight', ctypes.c_float), ('mask_weight', ctypes.c_float),
-                ('focal_alpha', ctypes.c_float), ('focal_gamma', ctypes.c_float), ('focal_eps', ctypes.c_float),
-                ('dice_eps', ctypes.c_float), ('dice_pred_min', ctypes.c_float), ('mask_pred_min', ctypes.c_float)]
-
-
-class VknAssignProblem(ctypes.Structure):
-    """Mirror of include/vkn.h: VknAssignProblem (device pointers as integers)."""
-    _fields_ = [('mask_logits', ctypes.c_void_p), ('cls_logits', ctypes.c_void_p), ('gt_masks', ctypes.c_void_p),
-                ('gt_labels', ctypes.c_void_p), ('G', ctypes.c_int), ('cost_out', ctypes.c_void_p)]
-
-
-class VknLsapProblem(ctypes.Structure):
-    """Mirror of include/vkn.h: VknLsapProblem (device pointers as integers)."""
-    _fields_ = [('cost', ctypes.c_void_p), ('nr', ctypes.c_int), ('nc', ctypes.c_int), ('gt_inds', ctypes.c_void_p),
-                ('row_ind', ctypes.c_void_p), ('col_ind', ctypes.c_void_p)]
-
-
-class VknTailImage(ctypes.Structure):
-    """Mirror of include/vkn.h: VknTailImage (device pointers as integers)."""
-    _fields_ = [('row_ind', ctypes.c_void_p), ('col_ind', ctypes.c_void_p), ('gt_labels', ctypes.c_void_p), ('sem_cls', ctypes.c_void_p),
-                ('k', ctypes.c_int), ('n_sem', ctypes.c_int), ('gt_row0', ctypes.c_int), ('sem_row0', ctypes.c_int),
-                ('pos0', ctypes.c_int), ('reserved', ctypes.c_int)]
-
-
-class VknTailCfg(ctypes.Structure):
-    """Mirror of include/vkn.h: VknTailCfg."""
-    _fields_ = [(n, ctypes.c_float) for n in ('w_cls', 'w_mask', 'w_dice', 'dice_eps', 'w_rank', 'avg_factor')] + [('with_rank', ctypes.c_int)]
-
-
-class VknTrackerCfg(ctypes.Structure):
-    """Mirror of include/vkn.h: VknTrackerCfg."""
-    _fields_ = ([(n, ctypes.c_float) for n in ('init_score_thr', 'obj_score_thr', 'match_score_thr', 'memo_momentum', 'memo_keep',
-                                               'nms_conf_thr', 'nms_backdrop_iou_thr', 'nms_class_iou_thr')]
-                + [(n, ctypes.c_int) for n in ('memo_tracklet_frames', 'memo_backdrop_frames', 'with_cats', 'match_metric', 'max_dets',
-                                               'max_tracklets', 'embed_dim')])
+HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn.h')
 
 
 class VknLibraryError(RuntimeError):
@@ -95,77 +26,126 @@ class VknError(RuntimeError):
         self.code = code
 
 
-_fp = ctypes.c_void_p  # device pointers travel as integers
+# ---- the reader of include/vkn.h.  Everything here that restates the C ABI (prototypes, struct mirrors, constants) is computed from
+#      the header by it, once per process.  It knows exactly the C subset the header is written in and refuses the rest.
+_SCALARS = {'int': ctypes.c_int, 'unsigned': ctypes.c_uint, 'unsigned int': ctypes.c_uint, 'size_t': ctypes.c_size_t,
+            'float': ctypes.c_float, 'double': ctypes.c_double, 'long long': ctypes.c_longlong}
+_POINTEES = {'void', 'char', 'unsigned char', 'int64_t'}     # types the header only ever points at
+_DECLARATOR = re.compile(r'([\w\s]*?)\s*((?:\*\s*(?:const\b\s*)?)*)(\w+)\s*(?:\[(\w+)\])?')
 
 
-class VknSplitItem(ctypes.Structure):
-    """include/vkn.h: one matrix of vkn_split_weights_batch_f32"""
-    _fields_ = [('W', ctypes.c_void_p), ('images', ctypes.c_void_p), ('ldn', ctypes.c_longlong), ('ldk', ctypes.c_longlong),
-                ('Nout', ctypes.c_int), ('K', ctypes.c_int), ('kvalid', ctypes.c_int), ('reserved', ctypes.c_int)]
-
-SPLIT_MAX_ITEMS = 64
-
-
-class VknDwItem(ctypes.Structure):
-    """include/vkn.h: one weight gradient of vkn_linear_dw_batch_f32"""
-    _fields_ = [('dY', ctypes.c_void_p), ('A', ctypes.c_void_p), ('dW', ctypes.c_void_p), ('db', ctypes.c_void_p),
-                ('ldy', ctypes.c_int), ('lda', ctypes.c_int), ('Nout', ctypes.c_int), ('K', ctypes.c_int)]
-
-DW_MAX_ITEMS = 48
+def _int(text, consts, where):
+    """`64`, `1u`, `0x000600`, `(-3)`, `(VKN_A | VKN_B)` -> int"""
+    total = 0
+    for term in text.strip('() \t').split('|'):
+        term = term.strip()
+        if not (term in consts or re.fullmatch(r'-?\d+|\d+u|0x[0-9a-fA-F]+', term)):
+            raise VknLibraryError(f'include/vkn.h: {where}: {text.strip()!r} is not an integer this binding can read')
+        total |= consts[term] if term in consts else int(term.rstrip('u'), 0)
+    return total
 
 
-class VknAdamwItem(ctypes.Structure):
-    """include/vkn.h: one work item of vkn_adamw_flat_f32 (a chunk of one parameter; device pointers as integers)"""
-    _fields_ = [('param', ctypes.c_void_p), ('grad', ctypes.c_void_p), ('exp_avg', ctypes.c_void_p), ('exp_avg_sq', ctypes.c_void_p),
-                ('n', ctypes.c_int), ('param_index', ctypes.c_int), ('group_index', ctypes.c_int), ('reserved', ctypes.c_int)]
-
-ADAMW_GROUP_ROW = 5     # VKN_ADAMW_GROUP_ROW: lr, weight_decay, beta1, beta2, eps (fp64)
-
-
-class VknUpdatorNorms(ctypes.Structure):
-    """include/vkn.h: LayerNorm vectors (and gate biases) of vkn_updator_mix_*"""
-    _fields_ = [(n, ctypes.c_void_p) for n in ('norm_in_w', 'norm_in_b', 'norm_out_w', 'norm_out_b', 'input_norm_in_w', 'input_norm_in_b',
-                                               'input_norm_out_w', 'input_norm_out_b', 'input_gate_b', 'update_gate_b')]
-
-
-class VknUpdatorNormGrads(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ('norm_in_w', 'norm_in_b', 'norm_out_w', 'norm_out_b', 'input_norm_in_w', 'input_norm_in_b',
-                                               'input_norm_out_w', 'input_norm_out_b')]
+def _declaration(decl, known, consts, where):
+    """One declaration, `const float *a, *b[VKN_N]` -> [(name, base type, pointer depth, array length or None)]"""
+    out, base = [], None
+    for part in decl.split(','):
+        m = _DECLARATOR.fullmatch(part.strip())
+        words = [w for w in m.group(1).split() if w != 'const'] if m else []
+        base = ' '.join(words) or base
+        if not m or bool(words) == bool(out) or base not in known:      # the type comes first, and only first
+            raise VknLibraryError(f'include/vkn.h: {where}: cannot read the declaration {" ".join(decl.split())!r}')
+        out.append((m.group(3), base, m.group(2).count('*'), m.group(4) and _int(m.group(4), consts, where)))
+    return out
 
 
-class VknDims(ctypes.Structure):
-    _fields_ = [('B', ctypes.c_int), ('N', ctypes.c_int), ('C', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
-                ('heads', ctypes.c_int), ('ff', ctypes.c_int), ('ncls', ctypes.c_int), ('n_cls_fcs', ctypes.c_int),
-                ('n_mask_fcs', ctypes.c_int), ('thr_logit', ctypes.c_float), ('ln_eps', ctypes.c_float)]
+def read_header(text):
+    """(prototypes, structs, constants) of a header written in vkn.h's C subset:
+    prototypes {function: ((base type, pointer depth) of the result, [(parameter, base type, pointer depth)])},
+    structs {name: [(field, base type, pointer depth, array length or None)]}, constants {VKN_*: int}; all in the header's order.
+    Raises VknLibraryError naming the declaration it cannot read."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    consts, structs, protos, known = {}, {}, {}, set(_SCALARS) | _POINTEES
+    for name, value in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(VKN_\w+)(.*)$', text, flags=re.M):
+        if value.strip():                                               # (the include guard has no value)
+            consts[name] = _int(value, consts, name)
+    text = re.sub(r'#ifdef __cplusplus.*?#endif', '', text, flags=re.S)
+    text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+
+    def struct(m):
+        structs[m.group(2)] = [f for d in m.group(1).split(';') if d.strip() for f in _declaration(d, known, consts, m.group(2))]
+        known.add(m.group(2))
+        return ''
+    text = re.sub(r'typedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;', struct, text)
+    for decl in filter(None, (' '.join(d.split()) for d in text.split(';'))):
+        m = re.fullmatch(r'([\w\s\*]+?)\b(vkn_\w+)\s*\(([^()]*)\)', decl)
+        if not m:
+            raise VknLibraryError(f'include/vkn.h: cannot read the declaration {decl[:120]!r}')
+        (_, rbase, rdepth, _), = _declaration(m.group(1) + ' result', known, consts, m.group(2))
+        params = [] if m.group(3).strip() == 'void' else [q for p in m.group(3).split(',') for q in _declaration(p, known, consts, m.group(2))]
+        if any(length is not None for *_, length in params):
+            raise VknLibraryError(f'include/vkn.h: {m.group(2)}: array parameters are not supported')
+        protos[m.group(2)] = ((rbase, rdepth), [q[:3] for q in params])
+    return protos, structs, consts
 
 
-_W_SCALAR_1 = ['ft_w', 'ft_b', 'ft_wT', 'dyn_w', 'dyn_b', 'inp_w', 'inp_b', 'ig_w', 'ig_b', 'ug_w', 'ug_b',
-               'norm_in_w', 'norm_in_b', 'norm_out_w', 'norm_out_b', 'inorm_in_w', 'inorm_in_b', 'inorm_out_w',
-               'inorm_out_b', 'fc_w', 'fc_b', 'fc_norm_w', 'fc_norm_b', 'attn_in_w', 'attn_in_b', 'attn_out_w',
-               'attn_out_b', 'attn_norm_w', 'attn_norm_b', 'ffn1_w', 'ffn1_b', 'ffn2_w', 'ffn2_b', 'ffn_norm_w',
-               'ffn_norm_b']
-_W_TAIL = ['pa_in_w', 'pa_in_b', 'pa_out_w', 'pa_out_b', 'pa_norm_w', 'pa_norm_b', 'lffn1_w', 'lffn1_b', 'lffn2_w',
-           'lffn2_b', 'lffn_norm_w', 'lffn_norm_b']
+with open(HEADER) as _f:
+    PROTOS, STRUCTS, CONSTS = read_header(_f.read())
+SYMBOLS = tuple(PROTOS)                     # every symbol include/vkn.h declares
+MAX_FCS = CONSTS['VKN_MAX_FCS']
+SPLIT_MAX_ITEMS = CONSTS['VKN_SPLIT_MAX_ITEMS']
+DW_MAX_ITEMS = CONSTS['VKN_DW_MAX_ITEMS']
+ADAMW_GROUP_ROW = CONSTS['VKN_ADAMW_GROUP_ROW']     # lr, weight_decay, beta1, beta2, eps (fp64)
+MIRRORS = {}                                # struct name -> ctypes.Structure, in the header's order
 
 
-class VknStageWeights(ctypes.Structure):
-    """Field order mirrors `struct VknStageWeights` in include/vkn.h exactly."""
-    _fields_ = ([(n, _fp) for n in _W_SCALAR_1]
-                + [('cls_fc_w', _fp * MAX_FCS), ('cls_ln_w', _fp * MAX_FCS), ('cls_ln_b', _fp * MAX_FCS),
-                   ('fc_cls_w', _fp), ('fc_cls_b', _fp),
-                   ('mask_fc_w', _fp * MAX_FCS), ('mask_ln_w', _fp * MAX_FCS), ('mask_ln_b', _fp * MAX_FCS),
-                   ('fc_mask_w', _fp), ('fc_mask_b', _fp)]
-                + [(n, _fp) for n in _W_TAIL]
-                + [('prepared', _fp), ('prepared_bytes', ctypes.c_size_t)])
+def _ctype(base, depth, where, result=False):
+    """Scalars by value; `const char*` results as bytes; a pointer to a mirrored struct typed; every other pointer (device memory, for the
+    most part) travels as an integer."""
+    if depth == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if depth == 1 and base == 'char' and result:
+        return ctypes.c_char_p
+    if depth == 1 and base in MIRRORS:
+        return ctypes.POINTER(MIRRORS[base])
+    if depth == 0:
+        raise VknLibraryError(f'include/vkn.h: {where}: {base!r} by value has no ctypes counterpart here')
+    return ctypes.c_void_p
 
 
-def hipcc_command(out=LIBPATH, extra=()):
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    return [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC', *extra,
-            *[os.path.join(CSRC, s) for s in SOURCES], '-o', out]
+for _name, _fields in STRUCTS.items():
+    MIRRORS[_name] = type(_name, (ctypes.Structure,), {
+        '__doc__': f'Mirror of include/vkn.h: {_name} (device pointers as integers).',
+        '_fields_': [(f, _ctype(b, d, _name) * n if n else _ctype(b, d, _name)) for f, b, d, n in _fields]})
+# importable by name: VknDims, VknStageWeights, VknSplitItem, VknDwItem, VknUpdatorNorms, VknUpdatorNormGrads, VknPanopticCfg, VknAssignCfg,
+# VknAssignProblem, VknLsapProblem, VknTailImage, VknTailCfg, VknAdamwItem, VknTrackerCfg
+globals().update(MIRRORS)
 
+# The pointer parameters that do NOT follow _ctype's rule: (function, parameter) -> ctypes type.
+POINTER_EXCEPTIONS = {
+    ('vkn_adamw_flat_f32', 'items'): ctypes.c_void_p,       # the VknAdamwItem array lives in DEVICE memory: callers pass tensor.data_ptr()
+    ('vkn_sum_n_f32', 'srcs'): ctypes.POINTER(ctypes.c_void_p),                   # a HOST array of device pointers, (c_void_p * n)(...)
+    ('vkn_qd_tracker_state_layout', 'offsets12'): ctypes.POINTER(ctypes.c_size_t),  # a HOST array the call fills, (c_size_t * 12)()
+}
+for _fn, _p in POINTER_EXCEPTIONS:
+    if _p not in [q[0] for q in PROTOS.get(_fn, ((), ()))[1]]:
+        raise VknLibraryError(f'POINTER_EXCEPTIONS names {_fn}({_p}), which include/vkn.h does not declare')
 
 DEBUG_LIBPATH = os.path.join(LIBDIR, 'libvkn_debug.so')
+
+
+def _hipcc(args, verbose=False, what='hipcc'):
+    cmd = [os.environ.get('HIPCC', '/opt/rocm/bin/hipcc'), '--offload-arch=gfx950', *args]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise VknLibraryError(f'{what} failed:\n' + r.stdout + r.stderr)
+
+
+def _shared_deps(debug):
+    """What every object depends on besides csrc/: the public header and, in the debug build, the kernel variants it #includes."""
+    exp = os.path.join(os.path.dirname(HERE), 'tools', 'experiments')
+    return [HEADER] + ([os.path.join(exp, f) for f in os.listdir(exp)] if debug and os.path.isdir(exp) else [])
 
 
 def _stale(path=None):
@@ -173,10 +153,7 @@ def _stale(path=None):
     if not os.path.exists(path):
         return True
     t = os.path.getmtime(path)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(os.path.dirname(HERE), 'include', 'vkn.h')]
-    exp = os.path.join(os.path.dirname(HERE), 'tools', 'experiments')     # debug-only kernel variants (#include'd under VKN_DEBUG)
-    if path == DEBUG_LIBPATH and os.path.isdir(exp):
-        deps += [os.path.join(exp, f) for f in os.listdir(exp)]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + _shared_deps(path == DEBUG_LIBPATH)
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 
@@ -185,11 +162,7 @@ def _compile_objects(objdir, extra=(), force=False, verbose=False):
     symbols exist, so plain separate compilation links)."""
     from concurrent.futures import ThreadPoolExecutor
     os.makedirs(objdir, exist_ok=True)
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + [os.path.join(os.path.dirname(HERE), 'include', 'vkn.h')]
-    exp = os.path.join(os.path.dirname(HERE), 'tools', 'experiments')
-    if '-DVKN_DEBUG' in extra and os.path.isdir(exp):
-        hdrs += [os.path.join(exp, f) for f in os.listdir(exp)]
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + _shared_deps('-DVKN_DEBUG' in extra)
     hdrs.append(os.path.join(CSRC, 'vkn_chain.hip'))              # vkn_chain_h2.hip #includes it
     t_h = max(os.path.getmtime(h) for h in hdrs if os.path.exists(h))
     jobs, objs = [], []
@@ -197,27 +170,14 @@ def _compile_objects(objdir, extra=(), force=False, verbose=False):
         src, obj = os.path.join(CSRC, s), os.path.join(objdir, s[:-4] + '.o')
         objs.append(obj)
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(t_h, os.path.getmtime(src)):
-            jobs.append([hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', *extra, '-c', src, '-o', obj])
-
-    def run(cmd):
-        if verbose:
-            print(' '.join(cmd), flush=True)
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise VknLibraryError('hipcc failed:\n' + r.stdout + r.stderr)
+            jobs.append(['-O3', '-std=c++17', '-fPIC', *extra, '-c', src, '-o', obj])
     with ThreadPoolExecutor(max_workers=max(1, min(int(os.environ.get('VKN_BUILD_JOBS', '6')), os.cpu_count() or 1))) as ex:
-        list(ex.map(run, jobs))
+        list(ex.map(lambda args: _hipcc(args, verbose), jobs))
     return objs
 
 
 def _link(objs, out, verbose=False):
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', *objs, '-o', out]
-    if verbose:
-        print(' '.join(cmd), flush=True)
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise VknLibraryError('hipcc link failed:\n' + r.stdout + r.stderr)
+    _hipcc(['-shared', '-fPIC', *objs, '-o', out], verbose, 'hipcc link')
 
 
 def build(force=False, verbose=False):
@@ -253,7 +213,7 @@ def use_debug():
 
 
 def lib():
-    """The loaded library (ctypes.CDLL) with argtypes set.  Raises VknLibraryError when it is not built."""
+    """The loaded library (ctypes.CDLL) with the header's prototypes set.  Raises VknLibraryError when it is not built."""
     global _LIB
     if _LIB is not None:
         return _LIB
@@ -262,252 +222,18 @@ def lib():
         raise VknLibraryError(f'{path} is missing — run `python -c "import __graft_entry__ as g; g.build()"` '
                               '(there is deliberately no CPU fallback)')
     L = ctypes.CDLL(path)
-    c_int, c_size, c_uint, c_float = ctypes.c_int, ctypes.c_size_t, ctypes.c_uint, ctypes.c_float
-    pD, pW = ctypes.POINTER(VknDims), ctypes.POINTER(VknStageWeights)
-    L.vkn_version.restype = c_int
-    L.vkn_version.argtypes = []
-    L.vkn_strerror.restype = ctypes.c_char_p
-    L.vkn_strerror.argtypes = [c_int]
-    L.vkn_sizeof_dims.restype = c_size
-    L.vkn_sizeof_dims.argtypes = []
-    L.vkn_sizeof_stage_weights.restype = c_size
-    L.vkn_sizeof_stage_weights.argtypes = []
-    if L.vkn_sizeof_dims() != ctypes.sizeof(VknDims) or L.vkn_sizeof_stage_weights() != ctypes.sizeof(VknStageWeights):
-        raise VknLibraryError('ctypes mirror of include/vkn.h structs is out of date (size mismatch)')
-    for fn in (L.vkn_workspace_init, L.vkn_workspace_status):
-        fn.restype = c_int
-        fn.argtypes = [_fp, c_size, _fp]
-    L.vkn_gather_workspace_bytes.restype = c_size
-    L.vkn_gather_workspace_bytes.argtypes = [c_int] * 4
-    L.vkn_mask_gather_f32.restype = c_int
-    L.vkn_mask_gather_f32.argtypes = [_fp, _fp, c_float, _fp, _fp, c_int, c_int, c_int, c_int, _fp, c_size, c_uint, _fp]
-    L.vkn_mask_gather_real_f32.restype = c_int
-    L.vkn_mask_gather_real_f32.argtypes = [_fp, _fp, _fp, _fp, c_int, c_int, c_int, c_int, _fp, c_size, _fp]
-    L.vkn_decode_workspace_bytes.restype = c_size
-    L.vkn_decode_workspace_bytes.argtypes = [c_int] * 3
-    L.vkn_mask_decode_f32.restype = c_int
-    L.vkn_mask_decode_f32.argtypes = [_fp, _fp, _fp, _fp, c_int, c_int, c_int, c_int, _fp, c_size, c_uint, _fp]
-    L.vkn_mask_decode_scaled_f32.restype = c_int
-    L.vkn_mask_decode_scaled_f32.argtypes = [_fp, _fp, _fp, _fp, _fp, c_int, c_int, c_int, c_int, _fp, c_size, c_uint, _fp]
-    L.vkn_split_planes_f32.restype = c_int
-    L.vkn_split_planes_f32.argtypes = [_fp, _fp, _fp, c_int, c_int, c_int, _fp]
-    L.vkn_mask_decode_planes_f32.restype = c_int
-    L.vkn_mask_decode_planes_f32.argtypes = [_fp, _fp, _fp, _fp, _fp, c_int, c_int, c_int, c_int, _fp]
-    L.vkn_decode_gather_supported.restype = c_int
-    L.vkn_decode_gather_supported.argtypes = [c_int, c_int]
-    L.vkn_mask_decode_planes_x.restype = c_int
-    L.vkn_mask_decode_planes_x.argtypes = [_fp, c_int, _fp, _fp, _fp, _fp, c_int, c_int, c_int, c_int, _fp]
-    L.vkn_decode_gather_x.restype = c_int
-    L.vkn_decode_gather_x.argtypes = [_fp, c_int, _fp, _fp, _fp, c_float, _fp, _fp, c_int, c_int, c_int, c_int, _fp, c_size, _fp]
-    L.vkn_decode_gather_f32.restype = c_int
-    L.vkn_decode_gather_f32.argtypes = [_fp, _fp, _fp, _fp, c_float, _fp, _fp, c_int, c_int, c_int, c_int, _fp, c_size, _fp]
-    L.vkn_track_link_f32.restype = c_int
-    L.vkn_track_link_f32.argtypes = [pD, pW, _fp, _fp, _fp, _fp, c_size, _fp]
-    L.vkn_track_link_flags_f32.restype = c_int
-    L.vkn_track_link_flags_f32.argtypes = [pD, pW, _fp, _fp, _fp, _fp, c_size, c_uint, _fp]
-    L.vkn_upsample_bilinear_f32.restype = c_int
-    L.vkn_upsample_bilinear_f32.argtypes = [_fp, _fp, c_int, c_int, c_int, c_int, _fp]
-    L.vkn_upsample_bilinear_f16out.restype = c_int
-    L.vkn_upsample_bilinear_f16out.argtypes = [_fp, _fp, c_int, c_int, c_int, c_int, _fp]
-    L.vkn_prepared_bytes.restype = c_size
-    L.vkn_prepared_bytes.argtypes = [pD, pW]
-    L.vkn_prepare_stage_f32.restype = c_int
-    L.vkn_prepare_stage_f32.argtypes = [pD, pW, _fp, c_size, _fp]
-    L.vkn_split_weight_f32.restype = c_int
-    L.vkn_split_weight_f32.argtypes = [_fp, _fp, c_int, c_int, _fp]
-    L.vkn_linear_f32.restype = c_int
-    L.vkn_linear_f32.argtypes = [_fp, _fp, _fp, _fp, _fp, c_int, c_int, c_int, c_int, c_int, _fp, c_size, _fp]
-    L.vkn_split_weight_t_f32.restype = c_int
-    L.vkn_split_weight_t_f32.argtypes = [_fp, _fp, c_int, c_int, _fp]
-    L.vkn_sizeof_split_item.restype = c_size
-    L.vkn_sizeof_split_item.argtypes = []
-    L.vkn_split_weights_batch_f32.restype = c_int
-    L.vkn_split_weights_batch_f32.argtypes = [ctypes.POINTER(VknSplitItem), c_int, _fp]
-    L.vkn_sizeof_dw_item.restype = c_size
-    L.vkn_sizeof_dw_item.argtypes = []
-    L.vkn_linear_dw_batch_f32.restype = c_int
-    L.vkn_linear_dw_batch_f32.argtypes = [ctypes.POINTER(VknDwItem), c_int, c_int, _fp]
-    for fn in (L.vkn_sizeof_updator_norms, L.vkn_sizeof_updator_norm_grads, L.vkn_sizeof_adamw_item):
-        fn.restype = c_size
-        fn.argtypes = []
-    # the host-side item arrays / parameter blocks are handed to the kernels verbatim: a header edit without its mirror is garbage pointers
-    for have, want, nm in ((L.vkn_sizeof_split_item(), ctypes.sizeof(VknSplitItem), 'VknSplitItem'), (L.vkn_sizeof_dw_item(), ctypes.sizeof(VknDwItem), 'VknDwItem'),
-                           (L.vkn_sizeof_updator_norms(), ctypes.sizeof(VknUpdatorNorms), 'VknUpdatorNorms'),
-                           (L.vkn_sizeof_updator_norm_grads(), ctypes.sizeof(VknUpdatorNormGrads), 'VknUpdatorNormGrads'),
-                           (L.vkn_sizeof_adamw_item(), ctypes.sizeof(VknAdamwItem), 'VknAdamwItem')):
-        if have != want:
-            raise VknLibraryError(f'ctypes mirror of include/vkn.h struct {nm} is out of date ({want} bytes here, {have} in the library)')
-    L.vkn_linear_dw_f32.restype = c_int
-    L.vkn_linear_dw_f32.argtypes = [_fp, c_int, _fp, c_int, _fp, _fp, c_int, c_int, c_int, c_int, _fp]
-    L.vkn_layernorm_act_fwd_f32.restype = c_int
-    L.vkn_layernorm_act_fwd_f32.argtypes = [_fp, c_int, _fp, c_int, _fp, _fp, c_float, c_int, _fp, c_int, _fp, c_int, c_int, _fp]
-    L.vkn_layernorm_act_bwd_f32.restype = c_int
-    L.vkn_layernorm_act_bwd_f32.argtypes = [_fp, c_int, _fp, c_int, _fp, c_int, _fp, _fp, _fp, c_int, _fp, c_int, _fp, _fp, c_int, c_int, _fp]
-    L.vkn_updator_gate_product_f32.restype = c_int
-    L.vkn_updator_gate_product_f32.argtypes = [_fp, _fp, _fp, c_int, c_int, _fp]
-    L.vkn_updator_gate_product_bwd_f32.restype = c_int
-    L.vkn_updator_gate_product_bwd_f32.argtypes = [_fp, _fp, _fp, _fp, _fp, c_int, c_int, _fp]
-    L.vkn_updator_mix_fwd_f32.restype = c_int
-    L.vkn_updator_mix_fwd_f32.argtypes = [_fp, _fp, _fp, ctypes.POINTER(VknUpdatorNorms), c_float, _fp, _fp, c_int, c_int, _fp]
-    L.vkn_updator_mix_bwd_f32.restype = c_int
-    L.vkn_updator_mix_bwd_f32.argtypes = [_fp, _fp, _fp, _fp, ctypes.POINTER(VknUpdatorNorms), _fp, _fp, _fp, _fp,
-                                          ctypes.POINTER(VknUpdatorNormGrads), c_int, c_int, _fp]
-    L.vkn_attention_f32.restype = c_int
-    L.vkn_attention_f32.argtypes = [_fp, c_int, _fp, _fp, c_int, _fp, c_int, c_int, c_int, c_int, c_int, c_int, _fp]
-    L.vkn_attention_bwd_f32.restype = c_int
-    L.vkn_attention_bwd_f32.argtypes = [_fp, c_int, _fp, _fp, c_int, _fp, c_int, _fp, c_int, _fp, c_int, _fp, _fp, c_int, c_int, c_int,
-                                        c_int, c_int, c_int, _fp]
-    L.vkn_kernel_updator_f32.restype = c_int
-    L.vkn_kernel_updator_f32.argtypes = [pD, pW, _fp, _fp, _fp, _fp, c_size, _fp]
-    L.vkn_stage_workspace_bytes.restype = c_size
-    L.vkn_stage_workspace_bytes.argtypes = [pD]
-    L.vkn_stage_forward_f32.restype = c_int
-    L.vkn_stage_forward_f32.argtypes = [pD, pW] + [_fp] * 9 + [_fp, c_size, c_uint, _fp]
-    L.vkn_stage_chain_f32.restype = c_int
-    L.vkn_stage_chain_f32.argtypes = [pD, pW] + [_fp] * 6 + [_fp, c_size, c_uint, _fp]
-    L.vkn_head_workspace_bytes.restype = c_size
-    L.vkn_head_workspace_bytes.argtypes = [pD]
-    L.vkn_focal_loss_blocks.restype = c_int
-    L.vkn_focal_loss_blocks.argtypes = [c_int, c_int]
-    L.vkn_focal_loss_f32.restype = c_int
-    L.vkn_focal_loss_f32.argtypes = [_fp, _fp, _fp, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp]
-    L.vkn_head_forward_f32.restype = c_int
-    L.vkn_head_forward_f32.argtypes = [pD, c_int, pW] + [_fp] * 8 + [c_int, _fp, _fp, c_size, c_uint, _fp]
-    L.vkn_head_forward_prof_f32.restype = c_int
-    L.vkn_head_forward_prof_f32.argtypes = [pD, c_int, pW] + [_fp] * 8 + [c_int, _fp, _fp, c_size, c_uint, _fp, _fp, _fp]
-    L.vkn_head_forward_link_f32.restype = c_int
-    L.vkn_head_forward_link_f32.argtypes = [pD, c_int, pW, pW, pW, c_int] + [_fp] * 8 + [c_int, _fp, _fp, c_size, c_uint, _fp]
-    L.vkn_stage_forward_link_f32.restype = c_int
-    L.vkn_stage_forward_link_f32.argtypes = [pD, pW, pW, pW, c_int] + [_fp] * 9 + [_fp, c_size, c_uint, _fp]
-    L.vkn_link_block_f32.restype = c_int
-    L.vkn_link_block_f32.argtypes = [pD, pW, _fp, _fp, _fp, _fp, _fp, c_size, _fp]
-    L.vkn_query_merge_workspace_bytes.restype = c_size
-    L.vkn_query_merge_workspace_bytes.argtypes = [pD, c_int]
-    L.vkn_query_merge_f32.restype = c_int
-    L.vkn_query_merge_f32.argtypes = [pD, c_int, pW, _fp, _fp, _fp, _fp, _fp, c_size, _fp]
-    L.vkn_conv_weight_bytes.restype = c_size
-    L.vkn_conv_weight_bytes.argtypes = [c_int] * 3
-    L.vkn_conv_prepare_f32.restype = c_int
-    L.vkn_conv_prepare_f32.argtypes = [_fp, c_int, c_int, c_int, _fp, c_size, _fp]
-    L.vkn_conv_gn_workspace_bytes.restype = c_size
-    L.vkn_conv_gn_workspace_bytes.argtypes = [c_int] * 6
-    L.vkn_conv_gn_f32.restype = c_int
-    L.vkn_conv_gn_f32.argtypes = [_fp] * 5 + [c_int, c_int, _fp, c_int, c_int, c_int, _fp, _fp] + [c_int] * 5 + [_fp, c_size, _fp]
-    L.vkn_localization_fpn_workspace_bytes.restype = c_size
-    L.vkn_localization_fpn_workspace_bytes.argtypes = [c_int] * 10
-    L.vkn_localization_fpn_f32.restype = c_int
-    L.vkn_localization_fpn_f32.argtypes = [_fp] * 8 + [c_int, _fp, _fp] + [c_int] * 10 + [_fp, c_size, _fp]
-    L.vkn_kernel_init_workspace_bytes.restype = c_size
-    L.vkn_kernel_init_workspace_bytes.argtypes = [c_int] * 5
-    L.vkn_kernel_init_f32.restype = c_int
-    L.vkn_kernel_init_f32.argtypes = [_fp] * 5 + [c_int, c_int, c_int, c_float] + [_fp] * 4 + [c_int] * 5 + [_fp, c_size, c_uint, _fp]
-    pP = ctypes.POINTER(VknPanopticCfg)
-    L.vkn_sizeof_panoptic_cfg.restype = c_size
-    L.vkn_sizeof_panoptic_cfg.argtypes = []
-    if L.vkn_sizeof_panoptic_cfg() != ctypes.sizeof(VknPanopticCfg):
-        raise VknLibraryError('ctypes mirror of VknPanopticCfg is out of date (size mismatch)')
-    L.vkn_panoptic_workspace_bytes.restype = c_size
-    L.vkn_panoptic_workspace_bytes.argtypes = [pP, c_int, c_int]
-    L.vkn_panoptic_joint_f32.restype = c_int
-    L.vkn_panoptic_joint_f32.argtypes = [pP, _fp, _fp, c_int, c_int, c_int, _fp, _fp, _fp, _fp, _fp, c_size, _fp]
-    L.vkn_merge_workspace_bytes.restype = c_size
-    L.vkn_merge_workspace_bytes.argtypes = [c_int, c_int]
-    L.vkn_panoptic_thing_first_u8.restype = c_int
-    L.vkn_panoptic_thing_first_u8.argtypes = [_fp, _fp, _fp, _fp, c_int, _fp, _fp, _fp, c_int, c_int, ctypes.c_double, ctypes.c_double,
-                                              c_int, _fp, _fp, _fp, _fp, c_size, _fp]
-    pA = ctypes.POINTER(VknAssignCfg)
-    L.vkn_sizeof_assign_cfg.restype = c_size
-    L.vkn_sizeof_assign_cfg.argtypes = []
-    if L.vkn_sizeof_assign_cfg() != ctypes.sizeof(VknAssignCfg):
-        raise VknLibraryError('ctypes mirror of VknAssignCfg is out of date (size mismatch)')
-    L.vkn_assign_workspace_bytes.restype = c_size
-    L.vkn_assign_workspace_bytes.argtypes = [c_int] * 3
-    L.vkn_assign_costs_f32.restype = c_int
-    L.vkn_assign_costs_f32.argtypes = [pA, _fp, _fp, _fp, _fp, c_int, c_int, c_int, c_int, _fp, _fp, c_size, _fp]
-    L.vkn_upsample_bilinear_bwd_f32.restype = c_int
-    L.vkn_upsample_bilinear_bwd_f32.argtypes = [_fp, _fp, c_int, c_int, c_int, c_int, _fp]
-    L.vkn_mask_losses_chunks.restype = c_int
-    L.vkn_mask_losses_chunks.argtypes = [c_int]
-    L.vkn_mask_losses_blocks.restype = c_int
-    L.vkn_mask_losses_blocks.argtypes = [c_int]
-    L.vkn_mask_losses_fwd_f32.restype = c_int
-    L.vkn_mask_losses_fwd_f32.argtypes = [_fp, _fp, _fp, _fp, c_int, c_int, c_int, c_int, c_int, _fp, _fp, _fp, _fp, _fp]
-    L.vkn_mask_losses_bwd_f32.restype = c_int
-    L.vkn_mask_losses_bwd_f32.argtypes = [_fp, _fp, _fp, _fp, _fp, _fp, _fp, c_int, c_int, c_int, c_int, _fp, _fp]
-    for fn, st in ((L.vkn_sizeof_tail_image, VknTailImage), (L.vkn_sizeof_tail_cfg, VknTailCfg)):
-        fn.restype = c_size
-        fn.argtypes = []
-        if fn() != ctypes.sizeof(st):
-            raise VknLibraryError(f'{st.__name__} layout mismatch between include/vkn.h and _lib.py')
-    L.vkn_stage_targets.restype = c_int
-    L.vkn_stage_targets.argtypes = [ctypes.POINTER(VknTailImage), c_int, c_int, c_int, c_int, c_int, ctypes.c_float] + [_fp] * 8
-    L.vkn_mask_losses_fwd_bank_f32.restype = c_int
-    L.vkn_mask_losses_fwd_bank_f32.argtypes = [_fp] * 5 + [c_int] * 5 + [_fp] * 5
-    L.vkn_stage_losses_final_f32.restype = c_int
-    L.vkn_stage_losses_final_f32.argtypes = [ctypes.POINTER(VknTailCfg), _fp, _fp, c_int, _fp, c_int, c_int, _fp, c_int, _fp, _fp, _fp,
-                                             c_int, c_int, c_int, _fp, _fp, _fp, _fp]
-    L.vkn_mask_losses_bwd_bank_f32.restype = c_int
-    L.vkn_mask_losses_bwd_bank_f32.argtypes = [_fp] * 9 + [ctypes.c_float] * 3 + [c_int, _fp, _fp, c_int, c_int, c_int, c_int, _fp, _fp]
-    L.vkn_mask_losses_lowres_chunks.restype = c_int
-    L.vkn_mask_losses_lowres_chunks.argtypes = [c_int, c_int]
-    L.vkn_mask_losses_fwd_lowres_f32.restype = c_int
-    L.vkn_mask_losses_fwd_lowres_f32.argtypes = [_fp] * 4 + [c_int] * 7 + [_fp] * 5
-    L.vkn_mask_losses_bwd_lowres_f32.restype = c_int
-    L.vkn_mask_losses_bwd_lowres_f32.argtypes = [_fp] * 9 + [ctypes.c_float] * 3 + [c_int, _fp, _fp] + [c_int] * 6 + [_fp, _fp]
-    L.vkn_scale_by_f32.restype = c_int
-    L.vkn_scale_by_f32.argtypes = [_fp, _fp, _fp, ctypes.c_float, _fp, c_size, _fp]
-    L.vkn_sgd_momentum_f32.restype = c_int
-    L.vkn_sgd_momentum_f32.argtypes = [_fp, _fp, _fp, c_size] + [ctypes.c_float] * 4 + [_fp]
-    L.vkn_adamw_workspace_bytes.restype = c_size
-    L.vkn_adamw_workspace_bytes.argtypes = [c_int] * 3
-    L.vkn_adamw_flat_f32.restype = c_int
-    L.vkn_adamw_flat_f32.argtypes = [_fp, c_int, c_int, _fp, c_int, _fp, _fp, c_float, _fp, _fp, _fp, c_size, _fp]
-    L.vkn_check_range_i64.restype = c_int
-    L.vkn_check_range_i64.argtypes = [_fp, c_size, ctypes.c_longlong, ctypes.c_longlong, c_int, _fp, _fp]
-    L.vkn_sum_n_f32.restype = c_int
-    L.vkn_sum_n_f32.argtypes = [ctypes.POINTER(ctypes.c_void_p), c_int, c_size, _fp, _fp]
-    L.vkn_pow2_scale_f32.restype = c_int
-    L.vkn_pow2_scale_f32.argtypes = [_fp, c_size, c_int, _fp, _fp, _fp]
-    L.vkn_scale_pad_rows_f32.restype = c_int
-    L.vkn_scale_pad_rows_f32.argtypes = [_fp, _fp, c_int, c_int, c_int, c_size, _fp, _fp]
-    L.vkn_transpose_pad_f32.restype = c_int
-    L.vkn_transpose_pad_f32.argtypes = [_fp, _fp, c_int, c_int, c_int, c_int, _fp, _fp]
-    L.vkn_threshold_rows_f16.restype = c_int
-    L.vkn_threshold_rows_f16.argtypes = [_fp, ctypes.c_float, c_int, c_int, c_int, c_size, _fp, _fp]
-    L.vkn_unscale_rows_f32.restype = c_int
-    L.vkn_unscale_rows_f32.argtypes = [_fp, _fp, _fp, c_int, c_int, c_int, c_int, _fp, _fp, _fp]
-    L.vkn_sizeof_assign_problem.restype = c_size
-    L.vkn_sizeof_assign_problem.argtypes = []
-    if L.vkn_sizeof_assign_problem() != ctypes.sizeof(VknAssignProblem):
-        raise VknLibraryError('VknAssignProblem layout mismatch between include/vkn.h and _lib.py')
-    L.vkn_assign_costs_batch_f32.restype = c_int
-    L.vkn_assign_costs_batch_f32.argtypes = [pA, ctypes.POINTER(VknAssignProblem), c_int, c_int, c_int, c_int, _fp, c_size, _fp]
-    L.vkn_assign_lowres_workspace_bytes.restype = c_size
-    L.vkn_assign_lowres_workspace_bytes.argtypes = [c_int] * 6
-    L.vkn_assign_costs_lowres_batch_f32.restype = c_int
-    L.vkn_assign_costs_lowres_batch_f32.argtypes = [pA, ctypes.POINTER(VknAssignProblem)] + [c_int] * 6 + [_fp, c_size, _fp]
-    L.vkn_sizeof_lsap_problem.restype = c_size
-    L.vkn_sizeof_lsap_problem.argtypes = []
-    if L.vkn_sizeof_lsap_problem() != ctypes.sizeof(VknLsapProblem):
-        raise VknLibraryError('VknLsapProblem layout mismatch between include/vkn.h and _lib.py')
-    L.vkn_lsap_batch_f32.restype = c_int
-    L.vkn_lsap_batch_f32.argtypes = [ctypes.POINTER(VknLsapProblem), c_int, _fp, _fp]
-    L.vkn_lsap_f32.restype = c_int
-    L.vkn_lsap_f32.argtypes = [_fp, c_int, c_int, _fp, _fp]
-    pT = ctypes.POINTER(VknTrackerCfg)
-    L.vkn_sizeof_tracker_cfg.restype = c_size
-    L.vkn_sizeof_tracker_cfg.argtypes = []
-    if L.vkn_sizeof_tracker_cfg() != ctypes.sizeof(VknTrackerCfg):
-        raise VknLibraryError('ctypes mirror of VknTrackerCfg is out of date (size mismatch)')
-    for fn in (L.vkn_qd_tracker_state_bytes, L.vkn_qd_tracker_workspace_bytes):
-        fn.restype = c_size
-        fn.argtypes = [pT]
-    L.vkn_qd_tracker_state_layout.restype = c_int
-    L.vkn_qd_tracker_state_layout.argtypes = [pT, ctypes.POINTER(ctypes.c_size_t)]
-    L.vkn_qd_tracker_reset.restype = c_int
-    L.vkn_qd_tracker_reset.argtypes = [pT, _fp, c_size, _fp]
-    L.vkn_qd_tracker_match_f32.restype = c_int
-    L.vkn_qd_tracker_match_f32.argtypes = [pT, _fp, c_size, _fp, _fp, _fp, c_int, c_int, _fp, _fp, _fp, _fp, _fp, c_size, _fp]
+    for name, (result, params) in PROTOS.items():
+        fn = getattr(L, name)
+        fn.restype = _ctype(*result, name, result=True)
+        fn.argtypes = [POINTER_EXCEPTIONS.get((name, p)) or _ctype(base, depth, name) for p, base, depth in params]
+    # header vs binary: structs are handed to the kernels verbatim, so a library built from another header means garbage pointers
+    for name, mirror in MIRRORS.items():
+        probe = 'vkn_sizeof_' + re.sub(r'(?<!^)(?=[A-Z])', '_', name[3:]).lower()
+        if probe not in PROTOS:
+            raise VknLibraryError(f'include/vkn.h declares struct {name} without its size probe {probe}()')
+        if getattr(L, probe)() != ctypes.sizeof(mirror):
+            raise VknLibraryError(f'{path} does not match include/vkn.h: struct {name} is {getattr(L, probe)()} bytes in the library, '
+                                  f'{ctypes.sizeof(mirror)} in the header')
     _LIB = L
     return L
 

@@ -13,18 +13,19 @@ import torch
 from . import _lib
 from ._lib import VknDims, VknStageWeights, check
 
-FLAG_REF_KERNELS = 1
-FLAG_EXACT_GEMM = 2
-FLAG_LOGITS_HANDOFF = 4
-FLAG_BITS_HANDOFF = 16
-FLAG_CHAIN_LAUNCHES = 256    # the [N x C] chain always as one launch per GEMM (default: by row count, include/vkn.h)
-FLAG_CHAIN_PERSISTENT = 512  # ... always as the two persistent row-owner kernels (vkn_chain.hip)
-FLAG_JOIN_EARLY = 32768     # head_forward: the side-stream link joins BEFORE the upsample (single-call latency; 1-3 % slower in throughput)
-FLAG_SCALED_F16 = 16384     # head_forward: the up-scaled logits as fp16 (vkn_upsample_bilinear_f16out)
-FLAG_CHAIN_BF16X3 = 65536   # ... the persistent kernels on the three-term bf16 split of rounds 2-4 (default since round 5: the two-term fp16 split, vkn_chain_h2.hip)
-FLAG_INIT_SEPARATE = 131072   # vkn_kernel_init_f32: the round-5 form of pass 0 (separate decodes + add + logits gather) instead of the one-pass kernel (A/B)
-FLAG_CHAIN_KSPLIT = 8192     # ... always as the few-row chain: column-spread GEMM phases, normalisation in the consumer (vkn_ksplit.hip)
-FLAG_SERIAL_LINK = 32   # tracking link on the caller's stream instead of the library's side stream (A/B; same results)
+_H = _lib.CONSTS      # the integer #defines of include/vkn.h
+FLAG_REF_KERNELS = _H['VKN_FLAG_REF_KERNELS']
+FLAG_EXACT_GEMM = _H['VKN_FLAG_EXACT_GEMM']
+FLAG_LOGITS_HANDOFF = _H['VKN_FLAG_LOGITS_HANDOFF']
+FLAG_BITS_HANDOFF = _H['VKN_FLAG_BITS_HANDOFF']
+FLAG_CHAIN_LAUNCHES = _H['VKN_FLAG_CHAIN_LAUNCHES']      # the [N x C] chain always as one launch per GEMM (default: by row count, include/vkn.h)
+FLAG_CHAIN_PERSISTENT = _H['VKN_FLAG_CHAIN_PERSISTENT']  # ... always as the two persistent row-owner kernels (vkn_chain.hip)
+FLAG_JOIN_EARLY = _H['VKN_FLAG_JOIN_EARLY']              # head_forward: the side-stream link joins BEFORE the upsample (single-call latency; 1-3 % slower in throughput)
+FLAG_SCALED_F16 = _H['VKN_FLAG_SCALED_F16']              # head_forward: the up-scaled logits as fp16 (vkn_upsample_bilinear_f16out)
+FLAG_CHAIN_BF16X3 = _H['VKN_FLAG_CHAIN_BF16X3']          # ... the persistent kernels on the three-term bf16 split of rounds 2-4 (default since round 5: the two-term fp16 split, vkn_chain_h2.hip)
+FLAG_INIT_SEPARATE = _H['VKN_FLAG_INIT_SEPARATE']        # vkn_kernel_init_f32: the round-5 form of pass 0 (separate decodes + add + logits gather) instead of the one-pass kernel (A/B)
+FLAG_CHAIN_KSPLIT = _H['VKN_FLAG_CHAIN_KSPLIT']          # ... always as the few-row chain: column-spread GEMM phases, normalisation in the consumer (vkn_ksplit.hip)
+FLAG_SERIAL_LINK = _H['VKN_FLAG_SERIAL_LINK']            # tracking link on the caller's stream instead of the library's side stream (A/B; same results)
 
 _tls = threading.local()
 
@@ -48,8 +49,8 @@ def _req(t, name):
     return t
 
 
-_X_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-FLAG_X_F16, FLAG_X_BF16 = 64, 128
+_X_DTYPES = {torch.float32: _H['VKN_X_F32'], torch.float16: _H['VKN_X_F16'], torch.bfloat16: _H['VKN_X_BF16']}
+FLAG_X_F16, FLAG_X_BF16 = _H['VKN_FLAG_X_F16'], _H['VKN_FLAG_X_BF16']
 
 
 def _req_x(t, name='x'):
@@ -463,7 +464,7 @@ def stage_chain(dims: VknDims, pack: StagePack, x_feat, obj_in, want_cls=True, f
     return cls, kern, kb, obj
 
 
-PHASE_A, PHASE_B, PHASE_C = 1024, 2048, 4096     # VKN_FLAG_PHASE_*: include/vkn.h
+PHASE_A, PHASE_B, PHASE_C = _H['VKN_FLAG_PHASE_A'], _H['VKN_FLAG_PHASE_B'], _H['VKN_FLAG_PHASE_C']
 
 
 def head_forward(dims: VknDims, packs, x, proposal_feats, mask_preds, prev_obj=None, upsample_stride=1, want_track=False,
@@ -502,7 +503,7 @@ def head_forward(dims: VknDims, packs, x, proposal_feats, mask_preds, prev_obj=N
         prev_obj = _req(clip_first_prev.reshape(1, N, C), 'clip_first_prev')
         if track is None:
             track = torch.empty((B, N, C), dtype=torch.float32, device=dev)
-        flags |= 8
+        flags |= _H['VKN_FLAG_CLIP_LINK']
     elif prev_obj is not None and (want_track or link_pre is not None):
         prev_obj = _req(prev_obj, 'previous_obj_feats')
         if want_track:
@@ -978,7 +979,7 @@ def unscale_rows(dk_p, dkb_p, scale, N):
     return dk, dkb
 
 
-SUM_MAX = 8
+SUM_MAX = _H['VKN_SUM_MAX']
 
 
 def sum_tensors(parts):
