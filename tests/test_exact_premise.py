@@ -1,0 +1,138 @@
+"""CPU: the premise of tests/test_gpu_exact.py, proved without a GPU.
+
+For every case of the sweep the case builders of exact_cases.py assert the PREMISE (max sum |terms| < 2^24 from the actual operands;
+fp16 outputs fit 11 bits) and NON-VACUITY (non-zero outputs, ON share in [0.05, 0.95], special rows as named).  Here, in addition,
+torch's own CPU fp32 op on the same operands — whose summation order is none of the orders the HIP kernels use — must equal the
+float64 reference bit for bit: with these operands fp32 accumulation is exact in any order."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import exact_cases as ec
+
+SWEEP = ec.bncp_sweep()
+
+
+def _same(got, want):
+    return got.dtype == torch.float32 and torch.equal(got.double(), want.double().reshape(got.shape))
+
+
+def test_sweep_covers_what_it_promises():
+    c = ec.sweep_covers()
+    assert c['N'] >= set(ec.N_EDGES) and c['C'] == set(ec.C_ALL) and c['P'] >= set(ec.P_EDGES) | set(ec.P_LARGE) and c['B'] == set(ec.B_ALL)
+    for C in (64, 256):
+        for N in ec.N_EDGES:
+            for P in ec.P_EDGES:
+                assert (C, N, P) in c['pairs'], (C, N, P)
+    for P in (62, 66, 126, 130, 135):                                  # ragged P as 1 x P and as H x W with W odd
+        assert (P, True) in c['forms'] and (P, False) in c['forms'], P
+        assert all(hw[1] % 2 == 1 for hw in ec.HW_OF[P][1:])
+    g = ec.gemm_shapes()
+    assert {m for m, _, _ in g} == set(ec.GEMM_M) and {k for _, k, _ in g} == set(ec.GEMM_K) and {n for _, _, n in g} == set(ec.GEMM_NOUT)
+    cs = ec.conv_shapes()
+    assert {c_[1] for c_ in cs} == {32, 64, 256} and {c_[0] for c_ in cs} == {1, 2, 3} and {(c_[2], c_[3]) for c_ in cs} == set(ec.CONV_SIZES)
+    assert {(c_[4], c_[5], c_[6]) for c_ in cs} == {(k, s, m) for k in (1, 3) for s in (1, 2) for m in ('raw', 'pos')}
+    assert any((W * S) % 4 for (_, _, _, W, S) in ec.UP_FWD)
+
+
+def test_special_rows_are_named():
+    rows = ec.special_rows(117, 135)
+    assert set(rows) == {'all_off', 'all_on', 'one_p0', 'one_plast', 'one_p63', 'one_p64', 'one_p127', 'one_p128'}
+    assert len({r for r, _ in rows.values()}) == len(rows)
+    assert set(ec.special_rows(31, 64)) == {'all_off', 'all_on', 'one_p0', 'one_plast', 'one_p63'}
+    assert ec.special_rows(1, 64) == {}
+
+
+def test_a_case_outside_the_premise_fails_as_a_test_bug():
+    with pytest.raises(ec.PremiseError):
+        ec.premise('too large', torch.tensor([2.0 ** 24]))
+    with pytest.raises(ec.PremiseError):
+        ec.non_vacuous('zero', torch.zeros(3))
+    with pytest.raises(ec.PremiseError):
+        ec.on_share('all on', torch.ones(8, dtype=torch.bool))
+    with pytest.raises(ec.PremiseError):
+        ec.premise_f16('12 bits', torch.tensor([2049.0]), 1.0)
+
+
+@pytest.mark.parametrize('C', [64, 256, 0], ids=['C64', 'C256', 'otherC_and_large'])
+def test_bncp_ops_fp32_equal_integer_reference(C):
+    for s in [s for s in SWEEP if (s.C == C if C else s.C not in (64, 256) or s.large)]:
+        x, z, xraw, cnt = ec.gather_case(s)
+        bits = (z >= ec.THR).float().flatten(2)
+        assert _same(torch.einsum('bnp,bcp->bnc', bits, x.flatten(2)), xraw), ('gather', s)
+        assert _same(bits.sum(-1), cnt), ('cnt', s)
+        for denom in ((1,) if s.large else (1, 16)):
+            x, a, out, asum = ec.gather_real_case(s, denom)
+            assert _same(torch.einsum('bnp,bcp->bnc', a.flatten(2), x.flatten(2)), out), ('gather_real', denom, s)
+            assert _same(a.flatten(2).sum(-1), asum), ('asum', denom, s)
+        x, k, kb, out = ec.decode_case(s)
+        assert _same(torch.einsum('bnc,bcp->bnp', k, x.flatten(2)) + kb[..., None], out), ('decode', s)
+        x, k, kb, zf, xraw, cnt = ec.fused_case(s)
+        z32 = torch.einsum('bnc,bcp->bnp', k, x.flatten(2)) + kb[..., None]
+        assert _same(z32, zf), ('fused logits', s)
+        assert _same(torch.einsum('bnp,bcp->bnc', (z32 >= ec.THR).float(), x.flatten(2)), xraw), ('fused', s)
+        if s.H * s.W % 64 == 0:                                   # the half-storage variants: integers up to 256 in fp16 and bf16
+            x, z, xraw, cnt = ec.gather_case(s, x_span=256)
+            assert torch.equal(x.half().float(), x) and torch.equal(x.bfloat16().float(), x), s
+
+
+def test_upscaling_fp32_and_fp16_equal_float64_reference():
+    for i, (B, N, H, W, S) in enumerate(ec.UP_FWD):
+        m, out = ec.up_case(B, N, H, W, S, 700 + i, f16=True)
+        got = F.interpolate(m, scale_factor=S, mode='bilinear', align_corners=False)
+        assert _same(got, out), (B, N, H, W, S)
+        assert torch.equal(got.half().double(), out)
+    for i, (B, N, H, W, S) in enumerate(ec.UP_BWD):
+        go, gin = ec.up_bwd_case(B, N, H, W, S, 800 + i)
+        z = torch.zeros((B, N, H, W), requires_grad=True)
+        F.interpolate(z, scale_factor=S, mode='bilinear', align_corners=False).backward(go)
+        assert _same(z.grad, gin), (B, N, H, W, S)
+    for i, (planes, H, W) in enumerate(ec.UP_PLANES[:2]):          # (the many-planes cases are tiny per plane: two of them here)
+        for S in (2, 4):
+            m, out = ec.up_case(1, planes, H, W, S, 900 + i, f16=True)
+            assert _same(F.interpolate(m, scale_factor=S, mode='bilinear', align_corners=False), out)
+
+
+def test_gemm_fp32_equals_integer_reference():
+    for i, (M, K, Nout) in enumerate(ec.gemm_shapes()):
+        A, W, b, y = ec.linear_case(M, K, Nout, 1100 + i, act=i % 2)
+        got = F.linear(A, W, b)
+        assert _same(got.clamp_min(0) if i % 2 else got, y), (M, K, Nout)
+    for i, (M, K, Nout) in enumerate([(117, 256, 256), (33, 64, 19), (513, 512, 124), (234, 2048, 256)]):
+        for act in (0, 1):
+            c = ec.linear_bwd_case(M, K, Nout, 1200 + i, act=act)
+            A, W = c['A'].clone().requires_grad_(True), c['W'].clone().requires_grad_(True)
+            b = c['b'].clone().requires_grad_(True)
+            y = F.linear(A, W, b)
+            y = y.relu() if act else y
+            y.backward(c['dy'])
+            assert _same(y.detach(), c['y']) and _same(A.grad, c['da']) and _same(W.grad, c['dW']) and _same(b.grad, c['db']), (M, K, Nout, act)
+
+
+def test_conv_fp32_equals_integer_reference():
+    for i, (B, C, H, W, ks, stride, mode) in enumerate(ec.conv_shapes()):
+        if H * W > 1000 and i % 4:                                 # the frame-sized maps: a quarter of them (they dominate the time)
+            continue
+        x, pos, w, out = ec.conv_case(B, C, H, W, ks, stride, mode, 1300 + i)
+        got = F.conv2d(x + pos if pos is not None else x, w, stride=stride, padding=ks // 2)
+        assert _same(got, out), (B, C, H, W, ks, stride, mode)
+
+
+def test_autograd_and_init_cases_hold():
+    for s in ec.GRAD_SHAPES:
+        x, k, kb, dz, dx, dk, dkb = ec.decode_grad_case(s)
+        xx, kk, bb = x.clone().requires_grad_(True), k.clone().requires_grad_(True), kb.clone().requires_grad_(True)
+        (torch.einsum('bnc,bcp->bnp', kk, xx.flatten(2)) + bb[..., None]).backward(dz.flatten(2))
+        assert _same(xx.grad, dx) and _same(kk.grad, dk) and _same(bb.grad, dkb), s
+        x, z, d, dx = ec.gather_grad_case(s)
+        xx = x.clone().requires_grad_(True)
+        torch.einsum('bnp,bcp->bnc', (z >= ec.THR).float().flatten(2), xx.flatten(2)).backward(d)
+        assert _same(xx.grad, dx), s
+    for i, sh in enumerate(ec.INIT_SHAPES):
+        for cat in (False, True):
+            loc, sem, iw, sw, sb, ref = ec.init_case(*sh, 1400 + i, cat)
+            mp = F.conv2d(loc, iw[:, :, None, None])
+            assert _same(mp, ref['mask_preds'][:, :iw.shape[0]]), sh
+            assert _same(F.conv2d(sem, sw[:, :, None, None], sb), ref['seg_preds']), sh
+            obj = torch.einsum('bnhw,bchw->bnc', (mp.sigmoid() > 0.5).float(), sem + loc)
+            assert _same(iw[None] + obj, ref['prop'][:, :iw.shape[0]]), sh
