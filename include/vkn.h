@@ -319,7 +319,11 @@ int vkn_layernorm_act_bwd_f32(const float* dy, int lddy, const float* in, int ld
  *      params / inputs: the packed outputs [M][2C] of dynamic_layer / input_layer (first half *_in, second half *_out);
  *      gate_feats [M][C] = param_in * input_in (:70); gates [M][2C] = [input_gate(gate_feats) | update_gate(gate_feats)] before their norms;
  *      features [M][C] = sigmoid(norm_in(update gate)) norm_out(param_out) + sigmoid(input_norm_in(input gate)) input_norm_out(input_out)
- *      (:74-90; gate_sigmoid=True, gate_norm_act=False — the shipped defaults); stats [M][8] for the backward.  C <= 256, C % 4 == 0.
+ *      (:74-90; gate_sigmoid=True, gate_norm_act=False — the shipped defaults); stats [M][8] = (mean, 1 / sqrt(var + eps)) of
+ *      norm_in(update gate), norm_out(param_out), input_norm_in(input gate), input_norm_out(input_out), for the backward.
+ *      Limits: C <= 256 for the mix kernels (any C: they read and write element-wise; VKN_E_SHAPE beyond); the gate-product kernels
+ *      move float4: C % 4 == 0 (VKN_E_SHAPE) and params / inputs / gate_feats / d_gate_feats / d_params / d_inputs 16-byte aligned
+ *      (VKN_E_ALIGN) — both checked before anything is launched.  Every operand is dense: row stride 2C ([M][2C]) or C ([M][C]).
  *      Backward: vkn_updator_mix_bwd_f32 writes d_gates [M][2C], the SECOND halves of d_params / d_inputs [M][2C] and the eight
  *      LayerNorm parameter gradients (d_norms may be NULL); vkn_updator_gate_product_bwd_f32 writes their FIRST halves from d_gate_feats. */
 typedef struct VknUpdatorNorms {
@@ -341,7 +345,9 @@ int vkn_updator_mix_bwd_f32(const float* d_features, const float* gates, const f
                             const VknUpdatorNormGrads* d_norms, int M, int C, void* stream);
 /*      the attention core of nn.MultiheadAttention: out[b][i][h] = softmax_j(q_i . k_j / sqrt(hd)) v_j per frame b and head h.
  *      Q rows b * Nq + i, K / V rows b * Nk + j; head h = columns [h * hd, (h + 1) * hd) of every operand; ld* = row strides
- *      (q, k, v may be column slices of one packed in_proj output).  hd in {4, 8, 16, 32, 64} for the backward, Nk <= 256.
+ *      (q, k, v may be column slices of one packed in_proj output).  Forward: hd a power of two in [4, 64], ldq / ldkv / ldo
+ *      multiples of 4, else VKN_E_SHAPE.  Backward: hd in {4, 8, 16, 32, 64}, Nk <= 256, else VKN_E_SHAPE (before any launch); dK and dV
+ *      share the row stride lddkv; any row strides >= the width.
  *      Backward: dQ, dK, dV from dO and the forward's O (the softmax is recomputed in fp32 from q, k). */
 int vkn_attention_f32(const float* Q, int ldq, const float* K, const float* V, int ldkv, float* out, int ldo, int B, int Nq, int Nk,
                       int heads, int hd, void* stream);

@@ -333,6 +333,35 @@ def linear_bwd_case(M, K, Nout, seed, act=0, wt=False):
     return dict(A=A, W=Wm.t().contiguous() if wt else Wm, b=b, dy=dy, y=y, da=da, dW=dW.t().contiguous() if wt else dW, db=db)
 
 
+# ---- the weight-gradient kernels called on their own (tests/test_gpu_chain_blocks.py): strided operands, accumulate, the batch form
+DW_SHAPES = [(1, 1, 1), (5, 33, 19), (117, 256, 19), (129, 64, 300), (468, 2048, 256), (3744, 256, 512)]
+DW_BATCH_M = 129
+DW_BATCH_ITEMS = (1, 3, 48)          # 48 = VKN_DW_MAX_ITEMS
+
+
+def dw_case(M, K, Nout, seed):
+    """dW = dy^T A, db = column sums of dy on integers in [-4, 4], and integer `old` values of dW / db in [-16, 16] for the accumulating
+    form: (dy [M, Nout], A [M, K], old_w [Nout, K], old_b [Nout], dW float64, db float64).  Premise: every sum of |terms|, the old
+    value included, stays below 2^24."""
+    g = gen(seed)
+    dy, A = ints((M, Nout), -4, 4, g), ints((M, K), -4, 4, g)
+    old_w, old_b = ints((Nout, K), -16, 16, g), ints((Nout,), -16, 16, g)
+    dy[0, 0], A[0, 0] = 3.0, 2.0
+    if float((dy.double().t() @ A.double())[0, 0]) == 0 or float(dy.double()[:, 0].sum()) == 0:   # (a 1 x 1 output is no coin toss)
+        dy[0, 0] = 4.0
+    dW, db = dy.double().t() @ A.double(), dy.double().sum(0)
+    name = f'dw M{M} K{K} N{Nout}'
+    premise(name, dy.double().abs().t() @ A.double().abs() + old_w.double().abs(), dy.double().abs().sum(0) + old_b.double().abs())
+    non_vacuous(name, dW, db)
+    return dy, A, old_w, old_b, dW, db
+
+
+def dw_batch_shapes(nitems):
+    """(K, Nout) of the items of a batch launch: ragged against the 64 x 128 tiles of the batch kernel"""
+    pool = [(33, 19), (64, 64), (128, 65), (1, 1), (129, 7), (256, 130), (40, 63)]
+    return [pool[i % len(pool)] for i in range(nitems)]
+
+
 # ---- FPN conv (the raw conv output of conv_gn; its statistics stay with the float rule of test_gpu_semantic_fpn.py)
 CONV_SIZES = ((1, 1), (2, 3), (3, 5), (12, 39), (47, 155), (48, 156))
 

@@ -194,3 +194,12 @@ def lowres_tail_reference(low, bank, tgt_row, rowk, S, w=(1.0, 4.0, 0.1), g=(1.0
     return dict(rows=torch.stack([bce, a, b, c], 1).detach(), lse=torch.logsumexp(z, 1).detach(), top=top.int(),
                 rank_sum=float(ce.detach().sum()), dice_a=a.detach(), dice_bc=((b + eps) + (c + eps)).detach(),
                 losses=tuple(float(v.detach()) for v in losses), grad=lo.grad)
+
+
+def run_and_kernels(fn):
+    """fn()'s result and the names of the device kernels it launched (torch.profiler records the library's launches as well)"""
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        out = fn()
+        torch.cuda.synchronize()
+    return out, {e.name for e in prof.events()}

@@ -109,6 +109,19 @@ def test_gemm_fp32_equals_integer_reference():
             assert _same(y.detach(), c['y']) and _same(A.grad, c['da']) and _same(W.grad, c['dW']) and _same(b.grad, c['db']), (M, K, Nout, act)
 
 
+def test_dw_fp32_equals_integer_reference():
+    """the cases of tests/test_gpu_chain_blocks.py's weight-gradient tests: plain, accumulating on integer old values, the batch items"""
+    cases = [(M, K, Nout, 1500 + i) for i, (M, K, Nout) in enumerate(ec.DW_SHAPES)]
+    cases += [(ec.DW_BATCH_M, K, Nout, 1600 + i) for i, (K, Nout) in enumerate(ec.dw_batch_shapes(max(ec.DW_BATCH_ITEMS)))]
+    for M, K, Nout, seed in cases:
+        dy, A, old_w, old_b, dW, db = ec.dw_case(M, K, Nout, seed)
+        assert _same(dy.t() @ A, dW) and _same(dy.sum(0), db), (M, K, Nout)
+        assert _same(old_w + dy.t() @ A, old_w.double() + dW) and _same(old_b + dy.sum(0), old_b.double() + db), (M, K, Nout)
+        w, b = torch.zeros(Nout, K, requires_grad=True), torch.zeros(Nout, requires_grad=True)
+        (F.linear(A, w, b) * dy).sum().backward()
+        assert _same(w.grad, dW) and _same(b.grad, db), (M, K, Nout)
+
+
 def test_conv_fp32_equals_integer_reference():
     for i, (B, C, H, W, ks, stride, mode) in enumerate(ec.conv_shapes()):
         if H * W > 1000 and i % 4:                                 # the frame-sized maps: a quarter of them (they dominate the time)

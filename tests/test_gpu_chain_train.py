@@ -2,6 +2,9 @@
 block forward AND backward against torch fp64 autograd of the same op, then the whole [B*N, C] chain (image head, the "ffn" tracking
 link, the previous_link "update" heads) against `KernelUpdateHead._chain_autograd`, the torch restatement of the reference lines
 (knet/kernel_updator.py:56-93, knet/det/kernel_update_head.py:198-227, knet/video/kernel_update_head.py:324-476).
+The blocks are reached here through their autograd wrappers at the chain's own shapes; `tests/test_gpu_chain_blocks.py` calls the
+same kernels through the C ABI and pins them element by element at every launch arm (the gated-update core on its own, every arm of
+the attention backward, NULL parameters, strides, tails, `accumulate`, the batch dW form).
 
 Tolerances (written where they are used): forward 2e-5 of the tensor's max-abs (bf16x3 split products, fp32 accumulation — the level
 of an fp32 GEMM); gradients 5e-5 of the max-abs for single ops, 5e-4 for the whole chain (a dozen layers deep, fp32 throughout).

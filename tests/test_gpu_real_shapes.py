@@ -11,7 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import PAN_CFG, assert_pan_matches_oracle
+from helpers import PAN_CFG, assert_pan_matches_oracle, run_and_kernels
 from oracle import synth
 from oracle.knet_oracle import panoptic_joint as oracle_panoptic_joint
 
@@ -177,15 +177,6 @@ def test_kitti_frame_upsample_vs_float64(vkn, S):
     assert out.shape == ref.shape and float((out.double() - ref).abs().max()) < 4e-6 * float(ref.abs().max())
 
 
-def _run_and_kernels(fn):
-    """fn()'s result and the names of the device kernels it launched (torch.profiler records the library's launches as well)"""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    return out, {e.name for e in prof.events()}
-
-
 def _has(names, kernel):
     return any(kernel in n for n in names)
 
@@ -212,12 +203,12 @@ def test_kitti_frame_default_policy(vkn, B, form):
         return all((u is None and v is None) or torch.equal(u, v) for u, v in zip(a, b))
     with torch.no_grad():
         run = lambda flags=0: head._head_forward(*ins, want_track=True, flags=flags)     # noqa: E731
-        a, names = _run_and_kernels(run)
+        a, names = run_and_kernels(run)
         assert same(a, outs)
         assert _has(names, 'k_fused_il'), sorted(n for n in names if n.startswith(('k_', 'void k_')))
         assert _has(names, FORM_KERNEL[form]), sorted(n for n in names if 'k_' in n)
         assert same(run(_chain_flags(vkn, form)), outs), f'the default call at {117 * B} rows is not the {form} chain'
         for fl in (ops.FLAG_BITS_HANDOFF, ops.FLAG_LOGITS_HANDOFF):
-            c, cn = _run_and_kernels(lambda: run(fl))
+            c, cn = run_and_kernels(lambda: run(fl))
             assert same(c, outs), fl
             assert not _has(cn, 'k_fused_il'), fl

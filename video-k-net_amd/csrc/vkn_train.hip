@@ -1206,9 +1206,12 @@ int vkn_layernorm_act_bwd_f32(const float* dy, int lddy, const float* in, int ld
     return VKN_OK;
 }
 
+static bool f4_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 int vkn_updator_gate_product_f32(const float* params, const float* inputs, float* gate_feats, int M, int C, void* stream) {
     if (!params || !inputs || !gate_feats || M <= 0 || C <= 0) return VKN_E_ARG;
     if (C % 4) return VKN_E_SHAPE;
+    if (!f4_aligned(params) || !f4_aligned(inputs) || !f4_aligned(gate_feats)) return VKN_E_ALIGN;   // (float4 loads / stores)
     hipLaunchKernelGGL(k_gprod_fwd, dim3((M * (C / 4) + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), params, inputs, 2 * C,
                        gate_feats, M, C);
     VKN_CHECK_LAUNCH();
@@ -1219,6 +1222,8 @@ int vkn_updator_gate_product_bwd_f32(const float* d_gate_feats, const float* par
                                      int M, int C, void* stream) {
     if (!d_gate_feats || !params || !inputs || !d_params || !d_inputs || M <= 0 || C <= 0) return VKN_E_ARG;
     if (C % 4) return VKN_E_SHAPE;
+    if (!f4_aligned(d_gate_feats) || !f4_aligned(params) || !f4_aligned(inputs) || !f4_aligned(d_params) || !f4_aligned(d_inputs))
+        return VKN_E_ALIGN;
     hipLaunchKernelGGL(k_gprod_bwd, dim3((M * (C / 4) + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), d_gate_feats, params,
                        inputs, 2 * C, d_params, d_inputs, M, C);
     VKN_CHECK_LAUNCH();
@@ -1275,7 +1280,7 @@ int vkn_attention_bwd_f32(const float* Q, int ldq, const float* K, const float* 
     if (!Q || !K || !V || !O || !dO || !dQ || !dK || !dV || B <= 0 || Nq <= 0 || Nk <= 0 || heads <= 0) return VKN_E_ARG;
     if (Nk > AB_THREADS / 2) return VKN_E_SHAPE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    {   // the matrix-core kernel where its LDS footprint fits (every shipped shape up to N = 128 at hd = 32, N = 224 at hd = 16)
+    {   // the matrix-core kernel where its LDS footprint fits (every shipped shape up to N = 128 at hd = 32; hd = 16 up to the backward's limit N = 256: 137 216 B)
         int rc = VKN_E_SHAPE;
         if (hd == 16) rc = attn_bwd_mfma_launch<16>(Q, ldq, K, V, ldkv, O, ldo, dO, lddo, dQ, lddq, dK, dV, lddkv, B, Nq, Nk, heads, st);
         else if (hd == 32) rc = attn_bwd_mfma_launch<32>(Q, ldq, K, V, ldkv, O, ldo, dO, lddo, dQ, lddq, dK, dV, lddkv, B, Nq, Nk, heads, st);
