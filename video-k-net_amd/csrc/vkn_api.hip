@@ -35,13 +35,55 @@ struct StageWs {
 // weights (everything else NULL).  It covers previous_link = "update_dynamic_cov" | "link_atten" (cur = the stage's incoming kernels:
 // the result REPLACES them, :324-372) and previous_type = "ffn" | "update" | "update_obj" (cur = the stage's updated kernels: the
 // result is the tracking embedding, :394-476).
-struct StageOpts {
+
+// One call of run_stage (StageCall).  Where the stage's masks come from and where they go:
+enum MasksFrom {
+    FROM_LOGITS,     // masks_in: fp32 logits, thresholded by the gather
+    FROM_BITS,       // bits_in (fused head only): bit(logit >= thr) words — the gather consumes nothing else, so intermediate stages never
+                     // write the 15.3 MB / frame of logits
+    FROM_GATHERED,   // s.xraw / s.cnt already hold the gather: the previous stage's fused decode -> gather pass left them there (or the caller did)
+    FROM_XFEAT       // xfeat_in (vkn_stage_chain_f32): the caller supplies x_feat — already feat-transformed and, for the clip-level VIS heads,
+                     // merged over the frames of a clip; no gather is launched, x is unused
+};
+enum MasksTo {
+    TO_LOGITS,    // masks_out: fp32 logits (final_decode; + the up-scaled output when up_out is given)
+    TO_BITS,      // bits_out: the hand-off as bit words
+    TO_GATHER,    // the NEXT stage's gather itself (fused head, default): this stage's decode and the next stage's gather run as one pass over
+                  // x (vkn_fused.hip) that leaves xraw / cnt in the shared workspace; neither logits nor bit words exist
+    TO_KERNELS,   // kern_out / kb_out (vkn_stage_chain_f32): the [B*N, C] chain alone — the folded fp32 decode kernels + bias, no decode
+    TO_NONE       // stop after the decode kernels (planes / kern32, kb) are written: the caller decodes (frame-sequential last stage)
+};
+struct StageCall {
+    // inputs
+    const VknStageWeights* w = nullptr;
+    const float *x = nullptr, *obj_in = nullptr;
+    // outputs (cls_logits may be NULL for stages without a classification branch)
+    float *obj_out = nullptr, *cls_logits = nullptr, *x_feat_out = nullptr;
+    bool cls_sigmoid = false;   // fused head, last stage: the caller wants cls_score.sigmoid() (knet/det/kernel_iter_head.py:307-308)
+    // hand-off in / out: the choice and the buffer it reads / writes
+    MasksFrom from = FROM_LOGITS;
+    const float *masks_in = nullptr, *xfeat_in = nullptr;
+    const unsigned* bits_in = nullptr;
+    MasksTo to = TO_LOGITS;
+    float* masks_out = nullptr;
+    unsigned* bits_out = nullptr;
+    // chain-only outputs (TO_KERNELS)
+    float *kern_out = nullptr, *kb_out = nullptr;
+    // events: prof0 / prof1 around the (first) decode launch of TO_LOGITS; obj_ready where obj_out is final
+    hipEvent_t prof0 = nullptr, prof1 = nullptr, obj_ready = nullptr;
+    // up-scale of the last stage (see final_decode)
+    float* up_out = nullptr;
+    int up_stride = 0, up_chunk = 0;
+    bool* up_done = nullptr;
+    // link options
+    const float* prev_obj = nullptr;              // previous-frame kernels of the tracking link; it runs when track_out is given too
+    float* track_out = nullptr;
     const VknStageWeights* link_pre = nullptr;    // previous_link block, applied to obj_in before the update
     const float* prev_pre = nullptr;              // its previous-frame kernels [B][N][C]
     const VknStageWeights* link_track = nullptr;  // previous_type "update" / "update_obj" block (NULL: the stage's own "ffn" link)
     int track_src = 0;                            // update feature of link_track's updator: 1 = x_feat, 2 = the stage's obj_out
-    bool skip_decode = false;                     // stop after the decode kernels (planes / kern32, kb) are written
     bool keep_xfeat = false;                      // materialise x_feat in the workspace: a caller-side link reads it after the stage
+    // cache warm-up
     const void* touch_next = nullptr;             // the NEXT stage's prepared weights: warmed by the reduction that ends this stage's
     size_t touch_next_bytes = 0;                  // fused decode -> gather pass (k_gather_reduce)
 };
@@ -74,13 +116,34 @@ struct PrepItem {
     const void** dst;
 };
 
-// enumerates (weight, shape, slot) in carve order; returns the number of items
-int prep_items(const VknDims* d, const VknStageWeights* w, PrepW* p, PrepItem* it) {
+// (nout, k) of fp16 image i of the persistent chain (VKN_H2_* order); nout == 0: the image does not exist
+struct H2Shape { int nout, k; };
+inline H2Shape h2_shape(const VknDims* d, const VknStageWeights* w, int i) {
     const int C = d->C, FF = d->ff;
+    switch (i) {
+        case VKN_H2_DYNFT: case VKN_H2_DYN: case VKN_H2_INP: return H2Shape{2 * C, C};
+        case VKN_H2_IN: return H2Shape{3 * C, C};
+        case VKN_H2_FFN1: return H2Shape{FF, C};
+        case VKN_H2_FFN2: return H2Shape{C, FF};
+        case VKN_H2_FCCLS: return H2Shape{w->fc_cls_w ? d->ncls : 0, C};
+        default: return H2Shape{C, C};
+    }
+}
+
+// shapes the chain kernels (vkn_chain.hip, vkn_ksplit.hip) are built for
+inline bool chain_width_ok(const VknDims* d) { return d->C == 256 && d->ff % 256 == 0 && d->ff <= 2048; }
+inline bool chain_shape_ok(const VknDims* d) { return chain_width_ok(d) && d->n_cls_fcs == 1 && d->n_mask_fcs == 1; }
+
+// assigns slots inside `base` (may be null: size query) in a fixed order; returns total bytes.  `it` / `n_out` (vkn_prepare_stage_f32):
+// the (weight, shape, slot) list of the plain pre-split copies, in carve order
+size_t carve_prepared(const VknDims* d, const VknStageWeights* w, char* base, PrepW* p, PrepItem* it = nullptr, int* n_out = nullptr) {
+    const int C = d->C, FF = d->ff;
+    Carver c{base, 0};
     int n = 0;
     auto add = [&](const float* src, int nout, int k, const void** dst) {
-        *dst = nullptr;
-        if (src) it[n++] = PrepItem{src, nout, k, dst};
+        *dst = src ? c.take<char>(vkn_split_w3_bytes(nout, k)) : nullptr;
+        if (src && it) it[n] = PrepItem{src, nout, k, dst};
+        if (src) ++n;
     };
     add(w->ft_w, C, C, &p->ft); add(w->ft_wT, C, C, &p->ftT);
     add(w->dyn_w, 2 * C, C, &p->dyn); add(w->inp_w, 2 * C, C, &p->inp);
@@ -95,40 +158,31 @@ int prep_items(const VknDims* d, const VknStageWeights* w, PrepW* p, PrepItem* i
     add(w->pa_in_w, C, C, &p->pa_in); add(w->pa_in_w ? w->pa_in_w + (size_t)C * C : nullptr, 2 * C, C, &p->pa_in_kv);
     add(w->pa_out_w, C, C, &p->pa_out);
     add(w->lffn1_w, FF, C, &p->lffn1); add(w->lffn2_w, C, FF, &p->lffn2);
-    return n;
-}
-
-// assigns slots inside `base` (may be null: size query); returns total bytes
-size_t carve_prepared(const VknDims* d, const VknStageWeights* w, char* base, PrepW* p, PrepItem* it, int* n_out) {
-    const int n = prep_items(d, w, p, it);
-    Carver c{base, 0};
-    for (int i = 0; i < n; ++i) *it[i].dst = c.take<char>(vkn_split_w3_bytes(it[i].nout, it[i].k));
     p->dynft = p->dec = nullptr;
     p->dynft32 = p->bcnt = p->dec32 = p->decb = p->dvec = p->kb0 = p->fmT = p->chain_consts = nullptr;
     if (has_composites(d, w)) {
-        const size_t C = d->C;
-        p->dynft = c.take<char>(vkn_split_w3_bytes(2 * d->C, d->C));
-        p->dec = c.take<char>(vkn_split_w3_bytes(d->C, d->C));
-        p->dynft32 = c.take<float>(2 * C * C);
-        p->bcnt = c.take<float>(2 * C);
-        p->dec32 = c.take<float>(C * C);
-        p->decb = c.take<float>(C);
-        p->dvec = c.take<float>(C);
+        const size_t Cs = d->C;
+        p->dynft = c.take<char>(vkn_split_w3_bytes(2 * C, C));
+        p->dec = c.take<char>(vkn_split_w3_bytes(C, C));
+        p->dynft32 = c.take<float>(2 * Cs * Cs);
+        p->bcnt = c.take<float>(2 * Cs);
+        p->dec32 = c.take<float>(Cs * Cs);
+        p->decb = c.take<float>(Cs);
+        p->dvec = c.take<float>(Cs);
         p->kb0 = c.take<float>(4);
-        p->fmT = c.take<float>(C * C);
-        if (d->C == 256 && d->ff <= 2048) p->chain_consts = c.take<float>(vkn_chain_consts_floats());
+        p->fmT = c.take<float>(Cs * Cs);
+        if (C == 256 && FF <= 2048) p->chain_consts = c.take<float>(vkn_chain_consts_floats());
     }
     for (int i = 0; i < VKN_H2_COUNT; ++i) p->h2[i] = nullptr;
     p->h2_scale = nullptr;
     p->h2_scratch = nullptr;
     // (shape conditions only: in a size query — base == NULL — every slot pointer is NULL)
-    if (has_composites(d, w) && d->C == 256 && d->ff <= 2048 && d->ff % 256 == 0 && d->n_cls_fcs == 1 && d->n_mask_fcs == 1 && w->inp_w && w->ig_w && w->ug_w && w->fc_w &&
-        w->attn_in_w && w->attn_out_w && w->ffn1_w && w->ffn2_w && w->cls_fc_w[0] && w->mask_fc_w[0]) {
-        const int C = d->C, FF = d->ff;
-        const int nout[VKN_H2_COUNT] = {2 * C, 2 * C, 2 * C, C, C, C, 3 * C, C, FF, C, C, C, w->fc_cls_w ? d->ncls : 0, C};
-        const int kk[VKN_H2_COUNT] = {C, C, C, C, C, C, C, C, C, FF, C, C, C, C};
-        for (int i = 0; i < VKN_H2_COUNT; ++i)
-            if (nout[i] > 0) p->h2[i] = c.take<char>(vkn_split_h2_bytes(nout[i], kk[i]));
+    if (has_composites(d, w) && chain_shape_ok(d) && w->inp_w && w->ig_w && w->ug_w && w->fc_w && w->attn_in_w && w->attn_out_w && w->ffn1_w &&
+        w->ffn2_w && w->cls_fc_w[0] && w->mask_fc_w[0]) {
+        for (int i = 0; i < VKN_H2_COUNT; ++i) {
+            const H2Shape h = h2_shape(d, w, i);
+            if (h.nout > 0) p->h2[i] = c.take<char>(vkn_split_h2_bytes(h.nout, h.k));
+        }
         p->h2_scale = c.take<float>(VKN_H2_COUNT * 8);
         p->h2_scratch = c.take<unsigned>(4);
     }
@@ -195,6 +249,30 @@ size_t carve_stage(const VknDims* d, char* base, StageWs* s) {
     s->lf = c.take<float>(M * C);
     s->kfh = c.take<_Float16>(B * NPT * C);
     s->kfl = c.take<_Float16>(B * NPT * C);
+    return (c.off + 255) & ~(size_t)255;
+}
+
+// the stage workspace in the caller's buffer: size check, alignment check, carve
+int stage_ws(const VknDims* d, void* ws, size_t ws_bytes, StageWs* s) {
+    if (!ws || ws_bytes < carve_stage(d, nullptr, s) || !aligned16(ws)) return VKN_E_WORKSPACE;
+    carve_stage(d, static_cast<char*>(ws), s);
+    return VKN_OK;
+}
+
+// workspace of the stand-alone gathers (partials per pixel group + the counts) and of the stand-alone decodes (the f16 planes)
+struct GatherWs { float *part, *cntp, *cnt; };
+size_t carve_gather(int B, int N, int C, int P, char* base, GatherWs* g) {
+    const size_t G = vkn_gather_groups(B, P), NPT = npt_of(N);
+    Carver c{base, 0};
+    g->part = c.take<float>((size_t)B * G * NPT * C);
+    g->cntp = c.take<float>((size_t)B * G * NPT);
+    g->cnt = c.take<float>((size_t)B * N);
+    return (c.off + 255) & ~(size_t)255;
+}
+size_t carve_planes(int B, int N, int C, char* base, _Float16** kfh, _Float16** kfl) {
+    Carver c{base, 0};
+    *kfh = c.take<_Float16>((size_t)B * npt_of(N) * C);
+    *kfl = c.take<_Float16>((size_t)B * npt_of(N) * C);
     return (c.off + 255) & ~(size_t)255;
 }
 
@@ -318,7 +396,7 @@ int run_updator(const VknDims* d, const VknStageWeights* w, const PrepW& pw, con
     return vkn_launch_gemm(s.f, nullptr, C, w->fc_w, pw.fc, M, C, C, 1, nullptr, e, st);           // :90-92
 }
 
-// link block (see StageOpts): video tracking link, previous_type == "ffn"      knet/video/kernel_update_head.py:394-415
+// link block (see StageCall): video tracking link, previous_type == "ffn"      knet/video/kernel_update_head.py:394-415
 //                                  previous_type == "update" / "update_obj"      :417-476   (updator on x_feat / on obj_feat)
 //                                  previous_link == "update_dynamic_cov"         :324-348   (updator on x_feat; out replaces obj_in)
 //                                  previous_link == "link_atten"                 :350-372
@@ -343,14 +421,33 @@ int run_link(const VknDims* d, const VknStageWeights* w, const PrepW& pw, const 
                    w->lffn_norm_b, out, st);
 }
 
+// the slots of w->prepared; none under VKN_FLAG_EXACT_GEMM (callers that use the pre-split weights whatever that flag says mask it)
 int carve_pw(const VknDims* d, const VknStageWeights* w, unsigned flags, PrepW* pw) {
     *pw = PrepW{};
-    if (w->prepared && !(flags & VKN_FLAG_EXACT_GEMM)) {
-        PrepItem items[40];
-        if (carve_prepared(d, w, static_cast<char*>(const_cast<void*>(w->prepared)), pw, items, nullptr) > w->prepared_bytes)
-            return VKN_E_WORKSPACE;
-    }
+    if (w->prepared && !(flags & VKN_FLAG_EXACT_GEMM) &&
+        carve_prepared(d, w, static_cast<char*>(const_cast<void*>(w->prepared)), pw) > w->prepared_bytes)
+        return VKN_E_WORKSPACE;
     return VKN_OK;
+}
+
+// The tracking link of a stage: the previous_type "update" (updator on x_feat) / "update_obj" (on `cur`) block `link_track`, or (NULL) the
+// stage's own "ffn" link in `w`                                                          knet/video/kernel_update_head.py:394-476
+int run_track_link(const VknDims* d, const StageWs& s, hipStream_t st, const float* cur, const float* prev, float* out,
+                   const VknStageWeights* w, const VknStageWeights* link_track, int track_src, const float* xfeat, unsigned flags) {
+    const VknStageWeights* lw = link_track ? link_track : w;
+    PrepW pw;
+    VKN_TRY(carve_pw(d, lw, flags, &pw));
+    return run_link(d, lw, pw, cur, prev, out, s, st, link_track ? (track_src == 2 ? cur : xfeat) : nullptr, flags);
+}
+
+// (i) mask gather of a stage into s.xraw / s.cnt              knet/det/kernel_update_head.py:190-195
+// `touch`: weights that the gather's reduction warms in the memory-side cache for the chain that follows it
+int run_gather(const VknDims* d, const float* x, const float* masks, const unsigned* bits, const StageWs& s, unsigned flags,
+               hipStream_t st, const void* touch = nullptr, size_t touch_bytes = 0) {
+    const int B = d->B, N = d->N, C = d->C, P = d->H * d->W, xdt = xdt_of(flags);
+    if (flags & VKN_FLAG_REF_KERNELS) return vkn_launch_gather_ref(x, masks, d->thr_logit, s.xraw, s.cnt, B, N, C, P, st);
+    if (bits) return vkn_launch_gather_bits(x, bits, s.xraw, s.cnt, s.part, s.cntp, B, N, C, P, st, xdt, s.status, touch, touch_bytes);
+    return vkn_launch_gather(x, masks, d->thr_logit, s.xraw, s.cnt, s.part, s.cntp, B, N, C, P, st, xdt, s.status, touch, touch_bytes);
 }
 
 // The LAST stage's logits decode from the planes in `s` (+ the caller's xS up-scaled output when up_out is given): in chunks of
@@ -388,6 +485,15 @@ inline int persistent_min_row_tiles(const PrepW& pw, unsigned flags) {
 inline unsigned pw_off(const VknStageWeights* w, const void* p) {
     return (unsigned)(static_cast<const char*>(p) - static_cast<const char*>(w->prepared));
 }
+// every chain form: the pre-split weights it streams — at 32-bit offsets into w->prepared — and the members its kernels take for granted
+inline bool chain_weights_ok(const PrepW& pw, bool have_cls) {
+    return pw.dynft && pw.dyn && pw.dec && pw.inp && pw.ig && pw.ug && pw.fc && pw.attn_in && pw.attn_out && pw.ffn1 && pw.ffn2 &&
+           pw.cls_fc[0] && pw.mask_fc[0] && (!have_cls || pw.fc_cls);
+}
+inline bool chain_stage_ok(const VknDims* d, const VknStageWeights* w, const PrepW& pw, bool have_cls) {
+    return chain_shape_ok(d) && w->prepared && w->prepared_bytes < (1ull << 31) && chain_weights_ok(pw, have_cls) && w->ffn1_w &&
+           w->cls_ln_w[0] && w->mask_ln_w[0];
+}
 bool chain_fast_ok(const VknDims* d, const VknStageWeights* w, const PrepW& pw, unsigned flags, bool have_cls) {
     if (flags & (VKN_FLAG_CHAIN_LAUNCHES | VKN_FLAG_EXACT_GEMM)) return false;
     if (vkn_dbg_env("VKN_CHAIN_LAUNCHES", 0)) return false;
@@ -403,14 +509,7 @@ bool chain_fast_ok(const VknDims* d, const VknStageWeights* w, const PrepW& pw, 
     if (!(flags & VKN_FLAG_CHAIN_PERSISTENT) && !vkn_dbg_env("VKN_CHAIN_PERSISTENT", 0) &&
         (d->B * d->N + 31) / 32 < persistent_min_row_tiles(pw, flags))
         return false;
-    if (d->C != 256 || d->n_cls_fcs != 1 || d->n_mask_fcs != 1 || d->ff % 256 != 0 || d->ff > 2048) return false;
-    if (!w->prepared || w->prepared_bytes >= (1ull << 31)) return false;
-    if (!pw.chain_consts || !pw.dynft || !pw.dyn || !pw.dec || !pw.inp || !pw.ig || !pw.ug || !pw.fc || !pw.attn_in || !pw.attn_out || !pw.ffn1 ||
-        !pw.ffn2 || !pw.cls_fc[0] || !pw.mask_fc[0])
-        return false;
-    if (have_cls && !pw.fc_cls) return false;
-    if (!w->ffn1_w || !w->cls_ln_w[0] || !w->mask_ln_w[0]) return false;
-    return true;
+    return pw.chain_consts && chain_stage_ok(d, w, pw, have_cls);
 }
 // the persistent chain runs on the two-term fp16 split (vkn_chain_h2.hip) wherever its images were prepared; VKN_FLAG_CHAIN_BF16X3 opts out
 inline bool chain_h2(const PrepW& pw, unsigned flags, bool have_cls) {
@@ -452,7 +551,7 @@ int run_chain_fast(const VknDims* d, const VknStageWeights* w, const PrepW& pw, 
     }
     c.consts = pw.chain_consts; c.kb0 = pw.kb0;
     c.ff = d->ff; c.ncls = d->ncls; c.cls_sigmoid = cls_sigmoid ? 1 : 0; c.eps = d->ln_eps; c.M = M;
-    c.obj_out = obj_out; c.cls_out = (w->fc_cls_w && cls_logits) ? cls_logits : nullptr; c.kb_out = s.kb;
+    c.obj_out = obj_out; c.cls_out = cls_logits; c.kb_out = s.kb;
     if (kern32_out) c.kern_out = kern32_out;
     else { c.plane_hi = s.kfh; c.plane_lo = s.kfl; }
     c.rows_per_frame = d->N; c.NPT = npt_of(d->N); c.status = s.status;
@@ -465,24 +564,19 @@ int run_chain_fast(const VknDims* d, const VknStageWeights* w, const PrepW& pw, 
 #define VKN_KS_MAX_ROW_TILES 16
 // The few-row chain (vkn_ksplit.hip): same shape conditions as the persistent chain, at most VKN_KS_MAX_ROW_TILES row tiles (or VKN_FLAG_CHAIN_KSPLIT),
 // every vector it reads with 16-byte loads aligned (parameters that are views into a packed buffer may not be).
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool ks_width_ok(const VknDims* d) {
+    return chain_width_ok(d) && (d->ff % 512 == 0 || d->ff <= 1024);   // at most four z-chunks of the FFN's second Linear
+}
 bool chain_ks_ok(const VknDims* d, const VknStageWeights* w, const PrepW& pw, unsigned flags, bool have_cls) {
     if (flags & (VKN_FLAG_CHAIN_LAUNCHES | VKN_FLAG_CHAIN_PERSISTENT | VKN_FLAG_EXACT_GEMM)) return false;
     if (vkn_dbg_env("VKN_CHAIN_LAUNCHES", 0) || vkn_dbg_env("VKN_CHAIN_PERSISTENT", 0) || !vkn_dbg_env("VKN_CHAIN_KSPLIT", 1)) return false;
     if (!(flags & VKN_FLAG_CHAIN_KSPLIT) && (d->B * d->N + 31) / 32 > VKN_KS_MAX_ROW_TILES) return false;
-    if (d->C != 256 || d->n_cls_fcs != 1 || d->n_mask_fcs != 1 || d->ff % 256 != 0 || d->ff > 2048) return false;
-    if (d->ff % 512 != 0 && d->ff > 1024) return false;   // at most four z-chunks of the FFN's second Linear
-    if (!w->prepared || w->prepared_bytes >= (1ull << 31)) return false;
-    if (!pw.dynft || !pw.dyn || !pw.dec || !pw.inp || !pw.ig || !pw.ug || !pw.fc || !pw.attn_in || !pw.attn_out || !pw.ffn1 || !pw.ffn2 ||
-        !pw.cls_fc[0] || !pw.mask_fc[0])
-        return false;
-    if (have_cls && !pw.fc_cls) return false;
-    if (!w->ffn1_w || !w->cls_ln_w[0] || !w->mask_ln_w[0]) return false;
+    if (!ks_width_ok(d) || !chain_stage_ok(d, w, pw, have_cls)) return false;
     const void* v16[] = {w->inorm_in_w, w->inorm_in_b, w->norm_in_w, w->norm_in_b, w->norm_out_w, w->norm_out_b, w->inorm_out_w, w->inorm_out_b,
                          w->fc_norm_w, w->fc_norm_b, w->attn_norm_w, w->attn_norm_b, w->ffn_norm_w, w->ffn_norm_b, w->ffn2_b,
                          w->cls_ln_w[0], w->cls_ln_b[0], w->mask_ln_w[0], w->mask_ln_b[0], pw.dvec};
     for (const void* p : v16)
-        if (!p || !al16(p)) return false;
+        if (!p || !aligned16(p)) return false;
     return true;
 }
 
@@ -564,7 +658,7 @@ int run_chain_ks(const VknDims* d, const VknStageWeights* w, const PrepW& pw, co
     if (obj_ready && hipEventRecord(obj_ready, st) != hipSuccess) return VKN_E_LAUNCH;
     // fc_cls(relu(LN(cls branch))) (+ sigmoid on the last stage) | folded decode kernels + bias from relu(LN(mask branch))     :217-227, :247
     int np = 0;
-    if (w->fc_cls_w && cls_logits) {
+    if (cls_logits) {
         pr[np] = ks_prob(s.lkv, 2 * C, pw.fc_cls, d->ncls, 8, eps);
         pr[np].pro.ln_w[0] = w->cls_ln_w[0]; pr[np].pro.ln_b[0] = w->cls_ln_b[0]; pr[np].pro.act = 1;
         pr[np].epi.bias = w->fc_cls_b; pr[np].epi.act = cls_sigmoid ? 2 : 0; pr[np].epi.out = cls_logits; pr[np].epi.ldo = d->ncls;
@@ -587,9 +681,9 @@ bool link_ks_ok(const VknDims* d, const VknStageWeights* w, const PrepW& pw, uns
     if (flags & (VKN_FLAG_CHAIN_LAUNCHES | VKN_FLAG_CHAIN_PERSISTENT | VKN_FLAG_EXACT_GEMM)) return false;
     if (vkn_dbg_env("VKN_CHAIN_LAUNCHES", 0) || !vkn_dbg_env("VKN_CHAIN_KSPLIT", 1)) return false;
     if (!(flags & VKN_FLAG_CHAIN_KSPLIT) && (d->B * d->N + 31) / 32 > VKN_KS_MAX_ROW_TILES) return false;
-    if (d->C != 256 || d->ff % 256 != 0 || d->ff > 2048 || (d->ff % 512 != 0 && d->ff > 1024)) return false;
+    if (!ks_width_ok(d)) return false;   // (a link block's dims say nothing about cls / mask FCs)
     if (!pw.pa_in || !pw.pa_in_kv || !pw.pa_out || !pw.lffn1 || !pw.lffn2) return false;
-    if (!w->pa_norm_w || !w->pa_norm_b || !al16(w->pa_norm_w) || !al16(w->pa_norm_b)) return false;
+    if (!w->pa_norm_w || !w->pa_norm_b || !aligned16(w->pa_norm_w) || !aligned16(w->pa_norm_b)) return false;
     return true;
 }
 
@@ -621,68 +715,62 @@ int run_link_ks(const VknDims* d, const VknStageWeights* w, const PrepW& pw, con
     return vkn_launch_rowepi(s.partial, zch, M, C, e, st);
 }
 
-int run_stage(const VknDims* d, const VknStageWeights* w, const float* x, const float* obj_in, const float* masks_in,
-              const float* prev_obj, float* cls_logits, float* masks_out, float* obj_out, float* x_feat_out,
-              float* track_out, const StageWs& s, unsigned flags, hipStream_t st, const unsigned* bits_in = nullptr,
-              unsigned* bits_out = nullptr, bool cls_sigmoid = false, bool gathered_in = false, bool gather_out = false,
-              hipEvent_t prof0 = nullptr, hipEvent_t prof1 = nullptr, const float* xfeat_in = nullptr, float* kern_out = nullptr,
-              float* kb_out = nullptr, hipEvent_t obj_ready = nullptr, float* up_out = nullptr, int up_stride = 0, int up_chunk = 0,
-              bool* up_done = nullptr, const StageOpts* so = nullptr) {
-    // xfeat_in / kern_out / kb_out (vkn_stage_chain_f32): the [B*N, C] chain alone — the caller supplies x_feat (already
-    // feat-transformed and, for the clip-level VIS heads, merged over the frames of a clip) and receives the folded fp32 decode
-    // kernels + bias instead of decoded masks; no gather and no decode are launched, x / masks_in / masks_out are unused.
-    // bits_in / bits_out (fused head only): the stage hand-off as bit words instead of fp32 logits — the gather consumes
-    // nothing but bit(logit >= thr), so intermediate stages never write the 15.3 MB / frame of logits.
-    // gather_out / gathered_in (fused head, default): the hand-off is the NEXT stage's gather itself — this stage's decode and the
-    // next stage's gather run as one pass over x (vkn_fused.hip) that leaves xraw / cnt in the shared workspace, where the next
-    // stage (gathered_in) finds them; neither logits nor bit words exist.
-    const int B = d->B, N = d->N, C = d->C, P = d->H * d->W, M = B * N;
+// Emits the stage's masks in the form c.to asks for, from the decode kernels — the f16 planes s.kfh / s.kfl, or fp32 `kern32` where the
+// exact decode runs (ref_decode) — and the folded decode bias `kb` (NULL: none).  `touch` / `touch_bytes`: see StageCall::touch_next.
+int emit_masks(const VknDims* d, const StageCall& c, const StageWs& s, bool ref_decode, const float* kern32, const float* kb,
+               const void* touch, size_t touch_bytes, unsigned flags, hipStream_t st) {
+    const int B = d->B, N = d->N, C = d->C, P = d->H * d->W, xdt = xdt_of(flags);
+    if (c.to == TO_KERNELS) {   // the kernels themselves are the output (already in c.kern_out)
+        if (c.kb_out && kb && hipMemcpyAsync(c.kb_out, kb, (size_t)B * N * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return VKN_E_LAUNCH;
+        return VKN_OK;
+    }
+    if (c.to == TO_NONE) return VKN_OK;   // the caller decodes all frames at once (frame-sequential last stage)
+    if (ref_decode) return vkn_launch_decode_ref(c.x, kern32, kb, c.masks_out, B, N, C, P, st);
+    if (c.to == TO_GATHER)
+        return vkn_launch_fused_decode_gather(c.x, s.kfh, s.kfl, kb, d->thr_logit, s.xraw, s.cnt, s.part, s.cntp, B, N, C, P, st, xdt, s.status,
+                                              touch, touch_bytes);
+    if (c.to == TO_BITS) return vkn_launch_decode_bits(c.x, s.kfh, s.kfl, kb, c.bits_out, d->thr_logit, B, N, C, P, st, xdt);
+    return final_decode(d, c.x, s, kb, c.masks_out, flags, st, c.prof0, c.prof1, c.up_out, c.up_stride, c.up_chunk, c.up_done);
+}
+
+int run_stage(const VknDims* d, const StageCall& c, const StageWs& s, unsigned flags, hipStream_t st) {
+    const VknStageWeights* w = c.w;
+    const int N = d->N, C = d->C, P = d->H * d->W, M = d->B * N;
     const bool ref = (flags & VKN_FLAG_REF_KERNELS) != 0;
-    const bool chain_only = kern_out != nullptr;
+    const bool chain_only = c.to == TO_KERNELS, given_xfeat = c.from == FROM_XFEAT;
     const bool ref_decode = ref || (P & 1) || chain_only;  // odd H*W: mask rows are not 8-byte aligned -> exact-fp32 FMA decode kernel
                                                            // (chain_only: fp32 folded kernels are the output)
     const bool has_ft = w->ft_w != nullptr;
-    const int xdt = xdt_of(flags);
-    const bool skip_decode = so && so->skip_decode;
-    const bool pre_link = so && so->link_pre && so->prev_pre;
-    const bool need_xfeat = (pre_link && so->link_pre->dyn_w) || (so && so->link_track && so->track_src == 1) || (so && so->keep_xfeat);  // (the link may run after the stage: side stream)
-    auto decode_final = [&](const float* kb) -> int {
-        return final_decode(d, x, s, kb, masks_out, flags, st, prof0, prof1, up_out, up_stride, up_chunk, up_done);
-    };
+    const bool have_cls = w->fc_cls_w && c.cls_logits;  // heads without a classification branch (knet_vis tracker stages with with_cls=False)
+    float* const cls_logits = have_cls ? c.cls_logits : nullptr;
+    const bool pre_link = c.link_pre && c.prev_pre;
+    const bool need_xfeat = (pre_link && c.link_pre->dyn_w) || (c.link_track && c.track_src == 1) || c.keep_xfeat;  // (the link may run after the stage: side stream)
     // half-storage x: the MFMA kernels only (whole 64-px tiles); the exact-fp32 reference kernels read fp32
-    if (xdt && !chain_only && (ref || (P % 64) != 0)) return VKN_E_SHAPE;
-    PrepW pw{};
-    if (w->prepared && !(flags & VKN_FLAG_EXACT_GEMM)) {
-        PrepItem items[40];
-        if (carve_prepared(d, w, static_cast<char*>(const_cast<void*>(w->prepared)), &pw, items, nullptr) > w->prepared_bytes)
-            return VKN_E_WORKSPACE;
-    }
+    if (xdt_of(flags) && !chain_only && (ref || (P % 64) != 0)) return VKN_E_SHAPE;
+    PrepW pw;
+    VKN_TRY(carve_pw(d, w, flags, &pw));
+    const bool comp = pw.dynft != nullptr;
+    const bool fewrow = comp && chain_ks_ok(d, w, pw, flags, have_cls), persistent = comp && chain_fast_ok(d, w, pw, flags, have_cls);
+    const bool fast = fewrow || persistent;
 
     // the gather's reduction warms the memory-side cache with the weights of the persistent chain that follows it
-    const bool will_fast = !xfeat_in && pw.dynft && chain_fast_ok(d, w, pw, flags, w->fc_cls_w && cls_logits) && vkn_dbg_env("VKN_CHAIN_TOUCH", 1);
-    const void* touch_own = will_fast ? w->prepared : nullptr;
-    const size_t touch_own_bytes = will_fast ? w->prepared_bytes : 0;
-    const void* touch_nx = (so && vkn_dbg_env("VKN_CHAIN_TOUCH", 1)) ? so->touch_next : nullptr;
-    const size_t touch_nx_bytes = touch_nx ? so->touch_next_bytes : 0;
-    // (i) mask gather                                        knet/det/kernel_update_head.py:190-195
-    if (gathered_in || xfeat_in) {
-        // s.xraw / s.cnt were produced by the previous stage's fused decode -> gather pass (or x_feat is given)
-    } else if (ref)
-        VKN_TRY(vkn_launch_gather_ref(x, masks_in, d->thr_logit, s.xraw, s.cnt, B, N, C, P, st));
-    else if (bits_in)
-        VKN_TRY(vkn_launch_gather_bits(x, bits_in, s.xraw, s.cnt, s.part, s.cntp, B, N, C, P, st, xdt, s.status, touch_own, touch_own_bytes));
-    else
-        VKN_TRY(vkn_launch_gather(x, masks_in, d->thr_logit, s.xraw, s.cnt, s.part, s.cntp, B, N, C, P, st, xdt, s.status, touch_own, touch_own_bytes));
+    const bool will_fast = !given_xfeat && persistent && vkn_dbg_env("VKN_CHAIN_TOUCH", 1);
+    const void* touch_nx = vkn_dbg_env("VKN_CHAIN_TOUCH", 1) ? c.touch_next : nullptr;
+    const size_t touch_nx_bytes = touch_nx ? c.touch_next_bytes : 0;
+    // (i) mask gather — unless s.xraw / s.cnt hold it already, or x_feat is given
+    if (c.from == FROM_LOGITS || c.from == FROM_BITS)
+        VKN_TRY(run_gather(d, c.x, c.masks_in, c.from == FROM_BITS ? c.bits_in : nullptr, s, flags, st, will_fast ? w->prepared : nullptr,
+                           will_fast ? w->prepared_bytes : 0));
 
     // folded feat_transform: x_feat = xraw . W_ft^T + cnt (x) b_ft             (:179-180 folded).  With the
     // composite weights x_feat itself is only materialised when the caller asks for it.
-    const bool comp = pw.dynft != nullptr;
-    float* xfeat = x_feat_out ? x_feat_out : s.xfeat;
+    float* xfeat = c.x_feat_out ? c.x_feat_out : s.xfeat;
     VknEpi e = mk_epi(d);
-    if (xfeat_in) {
-        xfeat = const_cast<float*>(xfeat_in);
+    if (given_xfeat) {
+        xfeat = const_cast<float*>(c.xfeat_in);
     } else if (has_ft) {
-        if (!comp || x_feat_out || need_xfeat) {
+        if (!comp || c.x_feat_out || need_xfeat) {
             e.bias = w->ft_b; e.rowscale = s.cnt; e.out = xfeat; e.ldo = C;
             VKN_TRY(vkn_launch_gemm(s.xraw, nullptr, C, w->ft_w, pw.ft, M, C, C, 1, nullptr, e, st));
         }
@@ -692,78 +780,59 @@ int run_stage(const VknDims* d, const VknStageWeights* w, const float* x, const 
     }
 
     // previous_link: the incoming kernels are rewritten from the previous frame's kernels first     knet/video/kernel_update_head.py:324-372
+    const float* obj_in = c.obj_in;
     if (pre_link) {
         PrepW pl;
-        VKN_TRY(carve_pw(d, so->link_pre, flags, &pl));
-        VKN_TRY(run_link(d, so->link_pre, pl, obj_in, so->prev_pre, s.lobj, s, st, so->link_pre->dyn_w ? xfeat : nullptr, flags));  // (link_atten: no updator)
+        VKN_TRY(carve_pw(d, c.link_pre, flags, &pl));
+        VKN_TRY(run_link(d, c.link_pre, pl, obj_in, c.prev_pre, s.lobj, s, st, c.link_pre->dyn_w ? xfeat : nullptr, flags));  // (link_atten: no updator)
         obj_in = s.lobj;
     }
 
     const float* kb = has_ft ? s.kb : nullptr;
-    const bool fewrow = comp && chain_ks_ok(d, w, pw, flags, w->fc_cls_w && cls_logits);
-    const bool fast = fewrow || (comp && chain_fast_ok(d, w, pw, flags, w->fc_cls_w && cls_logits));
+    float* const kern32 = ref_decode ? (chain_only ? c.kern_out : s.kern32) : nullptr;   // fp32 decode kernels instead of the f16 planes
+    const bool link = c.prev_obj && c.track_out;
     if (fast) {
         // (ii) + FC branches: few rows — nine column-spread GEMM phases + the attention (vkn_ksplit.hip); many rows — k_chain_a ->
         // attention -> k_chain_c (vkn_chain.hip); obj_out, cls, kb and the decode kernels are final
-        const bool raw = !xfeat_in;
+        const bool raw = !given_xfeat;
         if (fewrow) {
-            VKN_TRY(run_chain_ks(d, w, pw, raw ? s.xraw : xfeat, raw, s.cnt, obj_in, obj_out, cls_logits, cls_sigmoid,
-                                 ref_decode ? (chain_only ? kern_out : s.kern32) : nullptr, s, st, obj_ready));
+            VKN_TRY(run_chain_ks(d, w, pw, raw ? s.xraw : xfeat, raw, s.cnt, obj_in, c.obj_out, cls_logits, c.cls_sigmoid, kern32, s, st, c.obj_ready));
         } else {
-            VKN_TRY(run_chain_fast(d, w, pw, raw ? s.xraw : xfeat, raw, s.cnt, obj_in, obj_out, cls_logits, cls_sigmoid,
-                                   ref_decode ? (chain_only ? kern_out : s.kern32) : nullptr, s, st,
-                                   chain_h2(pw, flags, w->fc_cls_w && cls_logits)));
-            if (obj_ready && hipEventRecord(obj_ready, st) != hipSuccess) return VKN_E_LAUNCH;
+            VKN_TRY(run_chain_fast(d, w, pw, raw ? s.xraw : xfeat, raw, s.cnt, obj_in, c.obj_out, cls_logits, c.cls_sigmoid, kern32, s, st,
+                                   chain_h2(pw, flags, have_cls)));
+            if (c.obj_ready && hipEventRecord(c.obj_ready, st) != hipSuccess) return VKN_E_LAUNCH;
         }
-        if (chain_only) {
-            if (kb_out && hipMemcpyAsync(kb_out, s.kb, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return VKN_E_LAUNCH;
-        } else if (skip_decode) {
-        } else if (ref_decode) VKN_TRY(vkn_launch_decode_ref(x, s.kern32, kb, masks_out, B, N, C, P, st));
-        else if (gather_out)
-            VKN_TRY(vkn_launch_fused_decode_gather(x, s.kfh, s.kfl, kb, d->thr_logit, s.xraw, s.cnt, s.part, s.cntp, B, N, C, P, st, xdt, s.status, touch_nx, touch_nx_bytes));
-        else if (bits_out) VKN_TRY(vkn_launch_decode_bits(x, s.kfh, s.kfl, kb, bits_out, d->thr_logit, B, N, C, P, st, xdt));
-        else VKN_TRY(decode_final(kb));
-        if (prev_obj && track_out) {
-            if (so && so->link_track) {
-                PrepW pt;
-                VKN_TRY(carve_pw(d, so->link_track, flags, &pt));
-                VKN_TRY(run_link(d, so->link_track, pt, obj_out, prev_obj, track_out, s, st, so->track_src == 2 ? obj_out : xfeat, flags));
-            } else {
-                VKN_TRY(run_link(d, w, pw, obj_out, prev_obj, track_out, s, st, nullptr, flags));
-            }
-        }
+        VKN_TRY(emit_masks(d, c, s, ref_decode, s.kern32, kb, touch_nx, touch_nx_bytes, flags, st));
+        if (link) VKN_TRY(run_track_link(d, s, st, c.obj_out, c.prev_obj, c.track_out, w, c.link_track, c.track_src, xfeat, flags));
         return VKN_OK;
     }
 
     // (ii-a) KernelUpdator                                    knet/kernel_updator.py:56-93
-    VKN_TRY(run_updator(d, w, pw, xfeat, (comp && !xfeat_in) ? s.xraw : nullptr, s.cnt, obj_in, s.obj1, s, st));
+    VKN_TRY(run_updator(d, w, pw, xfeat, (comp && !given_xfeat) ? s.xraw : nullptr, s.cnt, obj_in, s.obj1, s, st));
 
     // (ii-b) kernel interaction: MHA + LN, FFN + LN           knet/det/kernel_update_head.py:204-215
     VKN_TRY(run_attention(d, s, s.obj1, s.obj1, d->heads, w->attn_in_w, pw.attn_in, nullptr, w->attn_in_b, w->attn_out_w,
                           pw.attn_out, w->attn_out_b, w->attn_norm_w, w->attn_norm_b, s.obj2, st));
-    const float* obj3 = s.obj2;
     if (w->ffn1_w) {
         VKN_TRY(run_ffn(d, s, s.obj2, w->ffn1_w, pw.ffn1, w->ffn1_b, w->ffn2_w, pw.ffn2, w->ffn2_b, w->ffn_norm_w,
-                        w->ffn_norm_b, obj_out, st));
-        obj3 = obj_out;
+                        w->ffn_norm_b, c.obj_out, st));
     } else {
-        if (hipMemcpyAsync(obj_out, s.obj2, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+        if (hipMemcpyAsync(c.obj_out, s.obj2, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
             return VKN_E_LAUNCH;
-        obj3 = obj_out;
     }
+    const float* obj3 = c.obj_out;
 
     // obj_out is final here: the fused head forks the tracking link onto its side stream at this point
     const bool fork_late = vkn_dbg_env("VKN_LINK_FORK_LATE", 0) != 0;  // debug A/B: 1 = fork the link behind the decode launch instead of at obj_out (measured: 8777 vs 8832 frames/s; the decode is equally fast either way)
-    if (obj_ready && !fork_late && hipEventRecord(obj_ready, st) != hipSuccess) return VKN_E_LAUNCH;
+    if (c.obj_ready && !fork_late && hipEventRecord(c.obj_ready, st) != hipSuccess) return VKN_E_LAUNCH;
 
     // cls and mask branches (:217-227) are independent: layer i of both runs as one grouped launch, then fc_cls + fc_mask
     // (the latter also emits the folded decode bias kb = mask_feat . b_ft).
     const float* tc = obj3;
     const float* tm = obj3;
     const int nl = d->n_cls_fcs > d->n_mask_fcs ? d->n_cls_fcs : d->n_mask_fcs;
+    VknGemmProb pr[2];
     for (int i = 0; i < nl; ++i) {
-        VknGemmProb pr[2];
         int np = 0;
         if (i < d->n_cls_fcs) {
             float* dst = (i & 1) ? s.t2 : s.t1;
@@ -780,91 +849,48 @@ int run_stage(const VknDims* d, const VknStageWeights* w, const float* x, const 
         }
         VKN_TRY(vkn_launch_gemm_group(pr, np, M, C, 1, nullptr, st));
     }
+    // where the decode kernels go: fp32 (the exact decode / the chain-only output) or the f16 planes
+    auto to_kernels = [&](VknEpi& ep) {
+        ep.ldo = C;
+        if (kern32) ep.out = kern32;
+        else { ep.plane_hi = s.kfh; ep.plane_lo = s.kfl; ep.rows_per_frame = N; ep.NPT = npt_of(N); }
+    };
+    int np = 0;
+    if (have_cls) {
+        e = mk_epi(d); e.bias = w->fc_cls_b; e.out = cls_logits; e.ldo = d->ncls;
+        if (c.cls_sigmoid) e.act = 2;
+        pr[np++] = VknGemmProb{tc, nullptr, nullptr, nullptr, C, w->fc_cls_w, pw.fc_cls, d->ncls, e};
+    }
+    const float* kern = s.kern32;   // what the exact decode reads
     if (comp) {
         // fc_cls, and the decode kernels Kf = fc_mask(.) . W_ft in ONE GEMM from the composite weight          (:221, :227, :247)
-        VknGemmProb pr[2];
-        int np = 0;
-        if (w->fc_cls_w && cls_logits) {  // heads without a classification branch (knet_vis tracker stages with with_cls=False)
-            e = mk_epi(d); e.bias = w->fc_cls_b; e.out = cls_logits; e.ldo = d->ncls;
-            if (cls_sigmoid) e.act = 2;  // fused head, last stage: the caller wants cls_score.sigmoid() (knet/det/kernel_iter_head.py:307-308)
-            pr[np++] = VknGemmProb{tc, nullptr, nullptr, nullptr, C, w->fc_cls_w, pw.fc_cls, d->ncls, e};
-        }
-        e = mk_epi(d); e.bias = pw.decb; e.ldo = C;
-        if (ref_decode) e.out = chain_only ? kern_out : s.kern32;
-        else { e.plane_hi = s.kfh; e.plane_lo = s.kfl; e.rows_per_frame = N; e.NPT = npt_of(N); }
+        e = mk_epi(d); e.bias = pw.decb; to_kernels(e);
         pr[np++] = VknGemmProb{tm, nullptr, nullptr, nullptr, C, pw.dec32, pw.dec, C, e};
         VKN_TRY(vkn_launch_gemm_group(pr, np, M, C, 1, nullptr, st));
-        if (chain_only) {
-            if (kb_out && hipMemcpyAsync(kb_out, s.kb, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return VKN_E_LAUNCH;
-        } else if (skip_decode) {
-            // the caller decodes all frames at once (frame-sequential last stage)
-        } else if (ref_decode) VKN_TRY(vkn_launch_decode_ref(x, s.kern32, kb, masks_out, B, N, C, P, st));
-        else if (gather_out)
-            VKN_TRY(vkn_launch_fused_decode_gather(x, s.kfh, s.kfl, kb, d->thr_logit, s.xraw, s.cnt, s.part, s.cntp, B, N, C, P, st, xdt, s.status, touch_nx, touch_nx_bytes));
-        else if (bits_out) VKN_TRY(vkn_launch_decode_bits(x, s.kfh, s.kfl, kb, bits_out, d->thr_logit, B, N, C, P, st, xdt));
-        else VKN_TRY(decode_final(kb));
     } else {
-        {
-            VknGemmProb pr[2];
-            int np = 0;
-            if (w->fc_cls_w && cls_logits) {
-                e = mk_epi(d); e.bias = w->fc_cls_b; e.out = cls_logits; e.ldo = d->ncls;
-                if (cls_sigmoid) e.act = 2;
-                pr[np++] = VknGemmProb{tc, nullptr, nullptr, nullptr, C, w->fc_cls_w, pw.fc_cls, d->ncls, e};
-            }
-            e = mk_epi(d); e.bias = w->fc_mask_b; e.out = (chain_only && !has_ft) ? kern_out : s.maskfeat; e.ldo = C;
-            if (has_ft) { e.dot_vec = w->ft_b; e.dot_out = s.kb; }
-            pr[np++] = VknGemmProb{tm, nullptr, nullptr, nullptr, C, w->fc_mask_w, pw.fc_mask, C, e};
-            VKN_TRY(vkn_launch_gemm_group(pr, np, M, C, 1, nullptr, st));
-        }
+        e = mk_epi(d); e.bias = w->fc_mask_b; e.out = (chain_only && !has_ft) ? c.kern_out : s.maskfeat; e.ldo = C;
+        if (has_ft) { e.dot_vec = w->ft_b; e.dot_out = s.kb; }
+        pr[np++] = VknGemmProb{tm, nullptr, nullptr, nullptr, C, w->fc_mask_w, pw.fc_mask, C, e};
+        VKN_TRY(vkn_launch_gemm_group(pr, np, M, C, 1, nullptr, st));
         // (iii) mask decode with the folded kernels  Kf = mask_feat . W_ft   :247-260
-        if (chain_only) {
-            if (has_ft) {
-                e = mk_epi(d); e.out = kern_out; e.ldo = C;
-                VKN_TRY(vkn_launch_gemm(s.maskfeat, nullptr, C, w->ft_wT, pw.ftT, M, C, C, 1, nullptr, e, st));
-                if (kb_out && hipMemcpyAsync(kb_out, s.kb, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-                    return VKN_E_LAUNCH;
-            } else if (kb_out && hipMemsetAsync(kb_out, 0, (size_t)M * sizeof(float), st) != hipSuccess) {
+        if (has_ft) {
+            e = mk_epi(d); to_kernels(e);
+            VKN_TRY(vkn_launch_gemm(s.maskfeat, nullptr, C, w->ft_wT, pw.ftT, M, C, C, 1, nullptr, e, st));
+        } else if (chain_only) {   // (no feat_transform: mask_feat is the kernel, written above; there is no decode bias)
+            if (c.kb_out && hipMemsetAsync(c.kb_out, 0, (size_t)M * sizeof(float), st) != hipSuccess) return VKN_E_LAUNCH;
+        } else if (!ref_decode) {
+            VKN_TRY(vkn_launch_split_planes(s.maskfeat, s.kfh, s.kfl, d->B, N, C, st));
+        } else if (c.to == TO_NONE) {   // the caller's decode reads s.kern32
+            if (hipMemcpyAsync(s.kern32, s.maskfeat, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
                 return VKN_E_LAUNCH;
-            }
-        } else if (ref_decode) {
-            const float* kern = s.maskfeat;
-            if (has_ft) {
-                e = mk_epi(d); e.out = s.kern32; e.ldo = C;
-                VKN_TRY(vkn_launch_gemm(s.maskfeat, nullptr, C, w->ft_wT, pw.ftT, M, C, C, 1, nullptr, e, st));
-                kern = s.kern32;
-            } else if (skip_decode) {
-                if (hipMemcpyAsync(s.kern32, s.maskfeat, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-                    return VKN_E_LAUNCH;
-            }
-            if (!skip_decode) VKN_TRY(vkn_launch_decode_ref(x, kern, kb, masks_out, B, N, C, P, st));
         } else {
-            if (has_ft) {
-                e = mk_epi(d); e.plane_hi = s.kfh; e.plane_lo = s.kfl; e.ldo = C; e.rows_per_frame = N; e.NPT = npt_of(N);
-                VKN_TRY(vkn_launch_gemm(s.maskfeat, nullptr, C, w->ft_wT, pw.ftT, M, C, C, 1, nullptr, e, st));
-            } else {
-                VKN_TRY(vkn_launch_split_planes(s.maskfeat, s.kfh, s.kfl, B, N, C, st));
-            }
-            if (skip_decode) {
-            } else if (gather_out)
-                VKN_TRY(vkn_launch_fused_decode_gather(x, s.kfh, s.kfl, kb, d->thr_logit, s.xraw, s.cnt, s.part, s.cntp, B, N, C, P,
-                                                       st, xdt, s.status, touch_nx, touch_nx_bytes));
-            else if (bits_out) VKN_TRY(vkn_launch_decode_bits(x, s.kfh, s.kfl, kb, bits_out, d->thr_logit, B, N, C, P, st, xdt));
-            else VKN_TRY(decode_final(kb));
+            kern = s.maskfeat;
         }
     }
+    VKN_TRY(emit_masks(d, c, s, ref_decode, kern, kb, touch_nx, touch_nx_bytes, flags, st));
 
-    if (obj_ready && fork_late && hipEventRecord(obj_ready, st) != hipSuccess) return VKN_E_LAUNCH;
-    if (prev_obj && track_out) {
-        if (so && so->link_track) {   // previous_type "update" (updator on x_feat) / "update_obj" (on obj_feat)        :417-476
-            PrepW pt;
-            VKN_TRY(carve_pw(d, so->link_track, flags, &pt));
-            VKN_TRY(run_link(d, so->link_track, pt, obj3, prev_obj, track_out, s, st, so->track_src == 2 ? obj3 : xfeat, flags));
-        } else {
-            VKN_TRY(run_link(d, w, pw, obj3, prev_obj, track_out, s, st, nullptr, flags));
-        }
-    }
+    if (c.obj_ready && fork_late && hipEventRecord(c.obj_ready, st) != hipSuccess) return VKN_E_LAUNCH;
+    if (link) VKN_TRY(run_track_link(d, s, st, obj3, c.prev_obj, c.track_out, w, c.link_track, c.track_src, xfeat, flags));
     return VKN_OK;
 }
 
@@ -934,12 +960,8 @@ const char* vkn_strerror(int code) {
 
 size_t vkn_gather_workspace_bytes(int B, int N, int C, int P) {
     if (B <= 0 || N <= 0 || C <= 0 || P <= 0) return 0;
-    const size_t G = vkn_gather_groups(B, P), NPT = npt_of(N);
-    Carver c{nullptr, 0};
-    c.take<float>((size_t)B * G * NPT * C);
-    c.take<float>((size_t)B * G * NPT);
-    c.take<float>((size_t)B * N);
-    return (c.off + 255) & ~(size_t)255;
+    GatherWs g;
+    return carve_gather(B, N, C, P, nullptr, &g);
 }
 
 int vkn_mask_gather_f32(const float* x, const float* mask_logits, float thr_logit, float* xraw_out, float* cnt_out, int B,
@@ -948,18 +970,15 @@ int vkn_mask_gather_f32(const float* x, const float* mask_logits, float thr_logi
     if (!aligned16(x) || !aligned16(mask_logits) || !aligned16(xraw_out)) return VKN_E_ALIGN;
     if (C % 32 != 0 || C > 256 || N > 256) return VKN_E_SHAPE;
     if (!ws || ws_bytes < vkn_gather_workspace_bytes(B, N, C, P)) return VKN_E_WORKSPACE;
-    const size_t G = vkn_gather_groups(B, P), NPT = npt_of(N);
-    Carver c{static_cast<char*>(ws), 0};
-    float* part = c.take<float>((size_t)B * G * NPT * C);
-    float* cntp = c.take<float>((size_t)B * G * NPT);
-    float* cnt = c.take<float>((size_t)B * N);
-    if (cnt_out) cnt = cnt_out;
+    GatherWs g;
+    carve_gather(B, N, C, P, static_cast<char*>(ws), &g);
+    float* cnt = cnt_out ? cnt_out : g.cnt;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (flags & VKN_FLAG_REF_KERNELS) {
         if (xdt_of(flags)) return VKN_E_SHAPE;
         return vkn_launch_gather_ref(x, mask_logits, thr_logit, xraw_out, cnt, B, N, C, P, st);
     }
-    return vkn_launch_gather(x, mask_logits, thr_logit, xraw_out, cnt, part, cntp, B, N, C, P, st, xdt_of(flags));
+    return vkn_launch_gather(x, mask_logits, thr_logit, xraw_out, cnt, g.part, g.cntp, B, N, C, P, st, xdt_of(flags));
 }
 
 int vkn_mask_gather_real_f32(const float* x, const float* a, float* out, float* asum_out, int B, int N, int C, int P, void* ws,
@@ -968,21 +987,15 @@ int vkn_mask_gather_real_f32(const float* x, const float* a, float* out, float* 
     if (!aligned16(x) || !aligned16(a) || !aligned16(out)) return VKN_E_ALIGN;
     if (C % 32 != 0 || C > 256 || N > 256) return VKN_E_SHAPE;
     if (!ws || ws_bytes < vkn_gather_workspace_bytes(B, N, C, P)) return VKN_E_WORKSPACE;
-    const size_t G = vkn_gather_groups(B, P), NPT = npt_of(N);
-    Carver c{static_cast<char*>(ws), 0};
-    float* part = c.take<float>((size_t)B * G * NPT * C);
-    float* cntp = c.take<float>((size_t)B * G * NPT);
-    float* asum = c.take<float>((size_t)B * N);
-    if (asum_out) asum = asum_out;
-    return vkn_launch_gather_real(x, a, out, asum, part, cntp, B, N, C, P, N, static_cast<hipStream_t>(stream));
+    GatherWs g;
+    carve_gather(B, N, C, P, static_cast<char*>(ws), &g);
+    return vkn_launch_gather_real(x, a, out, asum_out ? asum_out : g.cnt, g.part, g.cntp, B, N, C, P, N, static_cast<hipStream_t>(stream));
 }
 
 size_t vkn_decode_workspace_bytes(int B, int N, int C) {
     if (B <= 0 || N <= 0 || C <= 0) return 0;
-    Carver c{nullptr, 0};
-    c.take<_Float16>((size_t)B * npt_of(N) * C);
-    c.take<_Float16>((size_t)B * npt_of(N) * C);
-    return (c.off + 255) & ~(size_t)255;
+    _Float16 *kfh, *kfl;
+    return carve_planes(B, N, C, nullptr, &kfh, &kfl);
 }
 
 int vkn_mask_decode_f32(const float* x, const float* kernels, const float* bias, float* out, int B, int N, int C, int P,
@@ -996,9 +1009,8 @@ int vkn_mask_decode_f32(const float* x, const float* kernels, const float* bias,
         return vkn_launch_decode_ref(x, kernels, bias, out, B, N, C, P, st);
     }
     if (!ws || ws_bytes < vkn_decode_workspace_bytes(B, N, C)) return VKN_E_WORKSPACE;
-    Carver c{static_cast<char*>(ws), 0};
-    _Float16* kfh = c.take<_Float16>((size_t)B * npt_of(N) * C);
-    _Float16* kfl = c.take<_Float16>((size_t)B * npt_of(N) * C);
+    _Float16 *kfh, *kfl;
+    carve_planes(B, N, C, static_cast<char*>(ws), &kfh, &kfl);
     VKN_TRY(vkn_launch_split_planes(kernels, kfh, kfl, B, N, C, st));
     return vkn_launch_decode(x, kfh, kfl, bias, out, B, N, C, P, st, xdt_of(flags));
 }
@@ -1011,9 +1023,8 @@ int vkn_mask_decode_scaled_f32(const float* x, const float* kernels, const float
     if ((flags & VKN_FLAG_REF_KERNELS) || (P & 1)) return VKN_E_SHAPE;
     if (!ws || ws_bytes < vkn_decode_workspace_bytes(B, N, C)) return VKN_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    Carver c{static_cast<char*>(ws), 0};
-    _Float16* kfh = c.take<_Float16>((size_t)B * npt_of(N) * C);
-    _Float16* kfl = c.take<_Float16>((size_t)B * npt_of(N) * C);
+    _Float16 *kfh, *kfl;
+    carve_planes(B, N, C, static_cast<char*>(ws), &kfh, &kfl);
     VKN_TRY(vkn_launch_split_planes(kernels, kfh, kfl, B, N, C, st));
     return vkn_launch_decode_ex(x, kfh, kfl, bias, out, B, N, C, P, 0, N, st, xdt_of(flags), out_scale);
 }
@@ -1054,12 +1065,10 @@ int vkn_decode_gather_x(const void* xv, int x_dtype, const void* kf_hi, const vo
     if (!aligned16(x) || !aligned16(kf_hi) || !aligned16(kf_lo) || !aligned16(xraw_out)) return VKN_E_ALIGN;
     if (N > 256 || !vkn_fused_supported(C, P)) return VKN_E_SHAPE;
     if (!ws || ws_bytes < vkn_gather_workspace_bytes(B, N, C, P)) return VKN_E_WORKSPACE;
-    const size_t G = vkn_gather_groups(B, P), NPT = npt_of(N);
-    Carver c{static_cast<char*>(ws), 0};
-    float* part = c.take<float>((size_t)B * G * NPT * C);
-    float* cntp = c.take<float>((size_t)B * G * NPT);
+    GatherWs g;
+    carve_gather(B, N, C, P, static_cast<char*>(ws), &g);
     return vkn_launch_fused_decode_gather(x, static_cast<const _Float16*>(kf_hi), static_cast<const _Float16*>(kf_lo), bias,
-                                          thr_logit, xraw_out, cnt_out, part, cntp, B, N, C, P, static_cast<hipStream_t>(stream),
+                                          thr_logit, xraw_out, cnt_out, g.part, g.cntp, B, N, C, P, static_cast<hipStream_t>(stream),
                                           x_dtype);
 }
 
@@ -1074,15 +1083,9 @@ int vkn_track_link_flags_f32(const VknDims* d, const VknStageWeights* w, const f
     if (!w || !cur_obj || !prev_obj || !track_out) return VKN_E_ARG;
     if (!aligned16(cur_obj) || !aligned16(prev_obj) || !aligned16(track_out)) return VKN_E_ALIGN;
     StageWs s;
-    const size_t need = carve_stage(d, nullptr, &s);
-    if (!ws || ws_bytes < need || !aligned16(ws)) return VKN_E_WORKSPACE;
-    carve_stage(d, static_cast<char*>(ws), &s);
-    PrepW pw{};
-    if (w->prepared) {
-        PrepItem items[40];
-        if (carve_prepared(d, w, static_cast<char*>(const_cast<void*>(w->prepared)), &pw, items, nullptr) > w->prepared_bytes)
-            return VKN_E_WORKSPACE;
-    }
+    VKN_TRY(stage_ws(d, ws, ws_bytes, &s));
+    PrepW pw;
+    VKN_TRY(carve_pw(d, w, flags & ~VKN_FLAG_EXACT_GEMM, &pw));   // this entry point uses the pre-split weights under VKN_FLAG_EXACT_GEMM too
     return run_link(d, w, pw, cur_obj, prev_obj, track_out, s, static_cast<hipStream_t>(stream), nullptr, flags);
 }
 
@@ -1208,8 +1211,7 @@ int vkn_panoptic_joint_f32(const VknPanopticCfg* cfg, const float* cls_prob, con
 size_t vkn_prepared_bytes(const VknDims* d, const VknStageWeights* w) {
     if (check_dims(d) != VKN_OK || !w) return 0;
     PrepW pw;
-    PrepItem items[40];
-    return carve_prepared(d, w, nullptr, &pw, items, nullptr);
+    return carve_prepared(d, w, nullptr, &pw);
 }
 
 int vkn_prepare_stage_f32(const VknDims* d, const VknStageWeights* w, void* prepared, size_t bytes, void* stream) {
@@ -1242,17 +1244,15 @@ int vkn_prepare_stage_f32(const VknDims* d, const VknStageWeights* w, void* prep
         VKN_TRY(vkn_launch_split_w3(pw.dec32, const_cast<void*>(pw.dec), C, C, st));
         if (pw.h2_scale) {
             // the fp16-form images: per matrix its power-of-two scale (one launch, on the device), then the split of W * scale
-            const int C2 = d->C, FF = d->ff;
             const float* src[VKN_H2_COUNT] = {pw.dynft32, w->dyn_w, w->inp_w, w->ig_w, w->ug_w, w->fc_w, w->attn_in_w, w->attn_out_w, w->ffn1_w,
                                               w->ffn2_w, w->cls_fc_w[0], w->mask_fc_w[0], w->fc_cls_w, pw.dec32};
-            const int nout[VKN_H2_COUNT] = {2 * C2, 2 * C2, 2 * C2, C2, C2, C2, 3 * C2, C2, FF, C2, C2, C2, w->fc_cls_w ? d->ncls : 0, C2};
-            const int kk[VKN_H2_COUNT] = {C2, C2, C2, C2, C2, C2, C2, C2, C2, FF, C2, C2, C2, C2};
             if (hipMemsetAsync(pw.h2_scratch, 0, 4 * sizeof(unsigned), st) != hipSuccess) return VKN_E_LAUNCH;
             for (int i = 0; i < VKN_H2_COUNT; ++i) {
                 if (!pw.h2[i]) continue;
+                const H2Shape h = h2_shape(d, w, i);
                 float* sc = pw.h2_scale + 8 * i;
-                VKN_TRY(vkn_pow2_scale_f32(src[i], (size_t)nout[i] * kk[i], 10, sc, pw.h2_scratch, st));
-                VKN_TRY(vkn_launch_split_h2(src[i], const_cast<void*>(pw.h2[i]), nout[i], kk[i], sc, st));
+                VKN_TRY(vkn_pow2_scale_f32(src[i], (size_t)h.nout * h.k, 10, sc, pw.h2_scratch, st));
+                VKN_TRY(vkn_launch_split_h2(src[i], const_cast<void*>(pw.h2[i]), h.nout, h.k, sc, st));
             }
         }
         if (pw.chain_consts) {
@@ -1330,15 +1330,9 @@ int vkn_kernel_updator_f32(const VknDims* d, const VknStageWeights* w, const flo
     if (!w || !update_feature || !input_feature || !out) return VKN_E_ARG;
     if (!aligned16(update_feature) || !aligned16(input_feature) || !aligned16(out)) return VKN_E_ALIGN;
     StageWs s;
-    const size_t need = carve_stage(d, nullptr, &s);
-    if (!ws || ws_bytes < need || !aligned16(ws)) return VKN_E_WORKSPACE;
-    carve_stage(d, static_cast<char*>(ws), &s);
-    PrepW pw{};
-    if (w->prepared) {
-        PrepItem items[40];
-        if (carve_prepared(d, w, static_cast<char*>(const_cast<void*>(w->prepared)), &pw, items, nullptr) > w->prepared_bytes)
-            return VKN_E_WORKSPACE;
-    }
+    VKN_TRY(stage_ws(d, ws, ws_bytes, &s));
+    PrepW pw;
+    VKN_TRY(carve_pw(d, w, 0u, &pw));   // (no flags: always the pre-split weights)
     return run_updator(d, w, pw, update_feature, nullptr, nullptr, input_feature, out, s, static_cast<hipStream_t>(stream));
 }
 
@@ -1375,11 +1369,12 @@ int vkn_stage_forward_f32(const VknDims* d, const VknStageWeights* w, const floa
         return VKN_E_ALIGN;
     if (masks_in == masks_out) return VKN_E_ARG;
     StageWs s;
-    const size_t need = carve_stage(d, nullptr, &s);
-    if (!ws || ws_bytes < need || !aligned16(ws)) return VKN_E_WORKSPACE;
-    carve_stage(d, static_cast<char*>(ws), &s);
-    return run_stage(d, w, x, obj_in, masks_in, prev_obj, cls_logits, masks_out, obj_out, x_feat_out, track_out, s, flags,
-                     static_cast<hipStream_t>(stream));
+    VKN_TRY(stage_ws(d, ws, ws_bytes, &s));
+    StageCall c{};
+    c.w = w; c.x = x; c.obj_in = obj_in; c.masks_in = masks_in;
+    c.cls_logits = cls_logits; c.masks_out = masks_out; c.obj_out = obj_out; c.x_feat_out = x_feat_out;
+    c.prev_obj = prev_obj; c.track_out = track_out;
+    return run_stage(d, c, s, flags, static_cast<hipStream_t>(stream));
 }
 
 int vkn_stage_forward_link_f32(const VknDims* d, const VknStageWeights* w, const VknStageWeights* link_pre,
@@ -1395,17 +1390,14 @@ int vkn_stage_forward_link_f32(const VknDims* d, const VknStageWeights* w, const
         return VKN_E_ALIGN;
     if (masks_in == masks_out) return VKN_E_ARG;
     StageWs s;
-    const size_t need = carve_stage(d, nullptr, &s);
-    if (!ws || ws_bytes < need || !aligned16(ws)) return VKN_E_WORKSPACE;
-    carve_stage(d, static_cast<char*>(ws), &s);
-    StageOpts so;
-    so.link_pre = link_pre;
-    so.prev_pre = link_pre ? prev_obj : nullptr;
-    so.link_track = track_out ? link_track : nullptr;
-    so.track_src = track_src;
-    return run_stage(d, w, x, obj_in, masks_in, prev_obj, cls_logits, masks_out, obj_out, x_feat_out, track_out, s, flags,
-                     static_cast<hipStream_t>(stream), nullptr, nullptr, false, false, false, nullptr, nullptr, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, 0, 0, nullptr, &so);
+    VKN_TRY(stage_ws(d, ws, ws_bytes, &s));
+    StageCall c{};
+    c.w = w; c.x = x; c.obj_in = obj_in; c.masks_in = masks_in;
+    c.cls_logits = cls_logits; c.masks_out = masks_out; c.obj_out = obj_out; c.x_feat_out = x_feat_out;
+    c.prev_obj = prev_obj; c.track_out = track_out;
+    c.link_pre = link_pre; c.prev_pre = link_pre ? prev_obj : nullptr;
+    c.link_track = track_out ? link_track : nullptr; c.track_src = track_src;
+    return run_stage(d, c, s, flags, static_cast<hipStream_t>(stream));
 }
 
 int vkn_link_block_f32(const VknDims* d, const VknStageWeights* w, const float* update_feature, const float* cur,
@@ -1414,9 +1406,7 @@ int vkn_link_block_f32(const VknDims* d, const VknStageWeights* w, const float* 
     if (!w || !cur || !prev || !out || ((w->dyn_w != nullptr) != (update_feature != nullptr))) return VKN_E_ARG;
     if (!aligned16(cur) || !aligned16(prev) || !aligned16(out) || !aligned16(update_feature)) return VKN_E_ALIGN;
     StageWs s;
-    const size_t need = carve_stage(d, nullptr, &s);
-    if (!ws || ws_bytes < need || !aligned16(ws)) return VKN_E_WORKSPACE;
-    carve_stage(d, static_cast<char*>(ws), &s);
+    VKN_TRY(stage_ws(d, ws, ws_bytes, &s));
     PrepW pw;
     VKN_TRY(carve_pw(d, w, 0, &pw));
     return run_link(d, w, pw, cur, prev, out, s, static_cast<hipStream_t>(stream), update_feature);
@@ -1501,12 +1491,12 @@ int vkn_stage_chain_f32(const VknDims* d, const VknStageWeights* w, const float*
     if (!w || !x_feat || !obj_in || !kernels_out || !obj_out) return VKN_E_ARG;
     if (!aligned16(x_feat) || !aligned16(obj_in) || !aligned16(kernels_out) || !aligned16(obj_out)) return VKN_E_ALIGN;
     StageWs s;
-    const size_t need = carve_stage(d, nullptr, &s);
-    if (!ws || ws_bytes < need || !aligned16(ws)) return VKN_E_WORKSPACE;
-    carve_stage(d, static_cast<char*>(ws), &s);
-    return run_stage(d, w, nullptr, obj_in, nullptr, nullptr, cls_logits, nullptr, obj_out, nullptr, nullptr, s, flags,
-                     static_cast<hipStream_t>(stream), nullptr, nullptr, false, false, false, nullptr, nullptr, x_feat, kernels_out,
-                     kb_out);
+    VKN_TRY(stage_ws(d, ws, ws_bytes, &s));
+    StageCall c{};
+    c.w = w; c.obj_in = obj_in; c.cls_logits = cls_logits; c.obj_out = obj_out;
+    c.from = FROM_XFEAT; c.xfeat_in = x_feat;
+    c.to = TO_KERNELS; c.kern_out = kernels_out; c.kb_out = kb_out;
+    return run_stage(d, c, s, flags, static_cast<hipStream_t>(stream));
 }
 
 // Side stream of the fused head: the tracking link (attention over the previous frame's kernels + FFN, a latency-bound [N x C]
@@ -1660,24 +1650,27 @@ static int head_forward_impl(const VknDims* d, int num_stages, const VknStageWei
         // frames).  Everything that streams x stays batched; only ~15 small launches per frame are serialised.
         const float* prev_pre = (last && link_pre) ? prev_obj : nullptr;
         const bool seq = prev_pre && (flags & VKN_FLAG_CLIP_LINK) && (d->B > 1 || ph);
-        StageOpts so;
-        so.link_pre = prev_pre ? link_pre : nullptr;
-        so.prev_pre = prev_pre;
-        so.link_track = (last && track_out) ? link_track : nullptr;
-        so.track_src = track_src;
+        const VknStageWeights* ltrack = (last && track_out) ? link_track : nullptr;
+        StageCall c{};
+        c.w = &stages[sidx]; c.x = x; c.obj_in = o_in; c.obj_out = o_out;
+        c.cls_logits = last ? cls_prob : ctmp;
+        c.cls_sigmoid = last;   // the last stage's fc_cls epilogue applies the sigmoid and writes the caller's cls_prob directly
+        c.from = (use_fused && sidx > 0) ? FROM_GATHERED : (b_in ? FROM_BITS : FROM_LOGITS);
+        c.masks_in = m_in; c.bits_in = b_in;
+        c.link_pre = prev_pre ? link_pre : nullptr; c.prev_pre = prev_pre;
+        c.link_track = ltrack; c.track_src = track_src;
         if (!last && use_fused && !(flags & (VKN_FLAG_CHAIN_LAUNCHES | VKN_FLAG_EXACT_GEMM)) && stages[sidx + 1].prepared) {
             // the fused pass of this stage ends in the next stage's gather reduction: it warms the weight images the persistent kernels
             // will stream — the fp16 images alone where those run (they sit together in the prepared buffer)
             PrepW pwn;
-            PrepItem itn[40];
-            carve_prepared(d, &stages[sidx + 1], static_cast<char*>(const_cast<void*>(stages[sidx + 1].prepared)), &pwn, itn, nullptr);
+            (void)carve_pw(d, &stages[sidx + 1], flags, &pwn);   // (a buffer that is too small is the next stage's error)
             if ((flags & VKN_FLAG_CHAIN_PERSISTENT) || (d->B * d->N + 31) / 32 >= persistent_min_row_tiles(pwn, flags)) {
                 if (chain_h2(pwn, flags, false)) {
-                    so.touch_next = pwn.h2[VKN_H2_DYNFT];
-                    so.touch_next_bytes = (size_t)(reinterpret_cast<const char*>(pwn.h2_scale) - static_cast<const char*>(pwn.h2[VKN_H2_DYNFT]));
+                    c.touch_next = pwn.h2[VKN_H2_DYNFT];
+                    c.touch_next_bytes = (size_t)(reinterpret_cast<const char*>(pwn.h2_scale) - static_cast<const char*>(pwn.h2[VKN_H2_DYNFT]));
                 } else {
-                    so.touch_next = stages[sidx + 1].prepared;
-                    so.touch_next_bytes = stages[sidx + 1].prepared_bytes;
+                    c.touch_next = stages[sidx + 1].prepared;
+                    c.touch_next_bytes = stages[sidx + 1].prepared_bytes;
                 }
             }
         }
@@ -1685,37 +1678,33 @@ static int head_forward_impl(const VknDims* d, int num_stages, const VknStageWei
         hipEvent_t ev1 = last ? static_cast<hipEvent_t>(ev_decode_stop) : nullptr;
         float* up_out = (last && scaled_out && upsample_stride > 1) ? scaled_out : nullptr;
         if (!seq) {
-            // the last stage's fc_cls epilogue applies the sigmoid and writes the caller's cls_prob directly
-            VKN_TRY(run_stage(d, &stages[sidx], x, o_in, m_in, prev_in_stage, last ? cls_prob : ctmp, m_out, o_out, nullptr,
-                              prev_in_stage ? track_out : nullptr, s, flags, st, b_in, b_out, last, use_fused && sidx > 0,
-                              use_fused && !last, ev0, ev1, nullptr, nullptr, nullptr, (prev && side) ? side->fork : nullptr, up_out,
-                              upsample_stride, vkn_dbg_env("VKN_LAST_CHUNK", 0), &up_done, &so));
+            c.to = (use_fused && !last) ? TO_GATHER : (b_out ? TO_BITS : TO_LOGITS);
+            c.masks_out = m_out; c.bits_out = b_out;
+            c.prof0 = ev0; c.prof1 = ev1; c.obj_ready = (prev && side) ? side->fork : nullptr;
+            c.up_out = up_out; c.up_stride = upsample_stride; c.up_chunk = vkn_dbg_env("VKN_LAST_CHUNK", 0); c.up_done = &up_done;
+            c.prev_obj = prev_in_stage; c.track_out = prev_in_stage ? track_out : nullptr;
+            VKN_TRY(run_stage(d, c, s, flags, st));
         } else {
-            const VknStageWeights* w = &stages[sidx];
-            const int B = d->B, N = d->N, C = d->C, P = d->H * d->W;
-            if (do_a && !(use_fused && sidx > 0)) {  // the stage's gather for all frames (run_stage's step (i))
-                if (flags & VKN_FLAG_REF_KERNELS) VKN_TRY(vkn_launch_gather_ref(x, m_in, d->thr_logit, s.xraw, s.cnt, B, N, C, P, st));
-                else if (b_in) VKN_TRY(vkn_launch_gather_bits(x, b_in, s.xraw, s.cnt, s.part, s.cntp, B, N, C, P, st, xdt_of(flags), s.status));
-                else VKN_TRY(vkn_launch_gather(x, m_in, d->thr_logit, s.xraw, s.cnt, s.part, s.cntp, B, N, C, P, st, xdt_of(flags), s.status));
-            }
+            const int N = d->N, C = d->C;
+            // the stage's gather for all frames (run_stage's step (i)); its reduction warms no weights here
+            if (do_a && c.from != FROM_GATHERED) VKN_TRY(run_gather(d, x, m_in, b_in, s, flags, st));
             VknDims d1 = *d;
             d1.B = 1;
-            so.skip_decode = true;
-            so.keep_xfeat = so.link_track && so.track_src == 1;   // ... and reads every frame's x_feat ("update") from the workspace:
-            so.link_track = nullptr;  // the tracking link runs batched behind the loop (every frame's kernels are known then)
-            for (int b = 0; b < (do_b ? B : 0); ++b) {
+            c.from = FROM_GATHERED;
+            c.to = TO_NONE;   // one decode for all frames behind the loop
+            c.keep_xfeat = ltrack && track_src == 1;   // ... and reads every frame's x_feat ("update") from the workspace:
+            c.link_track = nullptr;  // the tracking link runs batched behind the loop (every frame's kernels are known then)
+            for (int b = 0; b < (do_b ? d->B : 0); ++b) {
                 const size_t r = (size_t)b * N;
                 const StageWs sb = frame_ws(s, d, b);
-                so.prev_pre = b == 0 ? prev_obj : o_out + (r - N) * C;
-                VKN_TRY(run_stage(&d1, w, x, o_in + r * C, nullptr, nullptr, cls_prob + r * d->ncls, nullptr, o_out + r * C, nullptr,
-                                  nullptr, sb, flags, st, nullptr, nullptr, true, true, false, nullptr, nullptr, nullptr, nullptr,
-                                  nullptr, nullptr, nullptr, 0, 0, nullptr, &so));
+                c.obj_in = o_in + r * C; c.obj_out = o_out + r * C; c.cls_logits = cls_prob + r * d->ncls;
+                c.prev_pre = b == 0 ? prev_obj : o_out + (r - N) * C;
+                VKN_TRY(run_stage(&d1, c, sb, flags, st));
             }
             if (!do_c) return VKN_OK;   // phases A / B end here: nothing was forked, nothing to join
             if (prev && side && hipEventRecord(side->fork, st) != hipSuccess) return VKN_E_LAUNCH;
-            VKN_TRY(final_decode(d, x, s, w->ft_w ? s.kb : nullptr, m_out, flags, st, ev0, ev1, up_out, upsample_stride,
+            VKN_TRY(final_decode(d, x, s, stages[sidx].ft_w ? s.kb : nullptr, m_out, flags, st, ev0, ev1, up_out, upsample_stride,
                                  vkn_dbg_env("VKN_LAST_CHUNK", 0), &up_done));
-            so.link_track = (last && track_out) ? link_track : nullptr;
         }
         m_in = m_out;
         o_in = o_out;
@@ -1741,12 +1730,9 @@ static int head_forward_impl(const VknDims* d, int num_stages, const VknStageWei
                     return VKN_E_LAUNCH;
                 pv = pvb;
             }
-            PrepW pw{};
-            const VknStageWeights* w = so.link_track ? so.link_track : &stages[sidx];
-            VKN_TRY(carve_pw(d, w, flags, &pw));
             // previous_type "update": the link's own KernelUpdator turns (x_feat, previous kernels) into the keys / values (:417-445);
             // s.xfeat of the last stage is still intact (nothing after the stage's feat-transform GEMM writes it)
-            VKN_TRY(run_link(d, w, pw, obj_out, pv, track_out, sl, ls, so.link_track ? (track_src == 2 ? obj_out : s.xfeat) : nullptr, flags));
+            VKN_TRY(run_track_link(d, sl, ls, obj_out, pv, track_out, &stages[sidx], ltrack, track_src, s.xfeat, flags));
             if (side) {
                 if (hipEventRecord(side->join, side->st) != hipSuccess) return VKN_E_LAUNCH;
                 joined = side;
