@@ -541,7 +541,8 @@ int vkn_panoptic_joint_f32(const VknPanopticCfg* cfg, const float* cls_prob, con
  *      distinct labels by descending score, one OR-ed mask per label; painted where still empty if that area >= stuff_max_area).
  *      All on the device (2 launches per mask, no host synchronisation); out: panoptic_seg [HW] int32 (0 = void),
  *      info [(Kt + Ks)][5] = per step {segment id or 0, kind 0 thing / 1 stuff, label, instance index (things) or area (stuff),
- *      score bits (things)}, nseg = number of segments.  ws: vkn_merge_workspace_bytes(Kt, Ks). */
+ *      score bits (things)}, nseg = number of segments.  ws: vkn_merge_workspace_bytes(Kt, Ks).  Kt == 0 / Ks == 0: the pointers of
+ *      that side are not read and may be NULL (so may `info` when both are 0: the map is cleared, nseg = 0). */
 size_t vkn_merge_workspace_bytes(int Kt, int Ks);
 int vkn_panoptic_thing_first_u8(const unsigned char* thing_masks, const float* thing_scores, const int* thing_labels,
                                 const int* thing_order, int Kt, const unsigned char* stuff_masks, const int* stuff_labels,

@@ -377,6 +377,93 @@ def run_pan_thing_first(name, p):
     print(f'{name}: ok  segments per frame = {nseg}  void = {float((np.stack(segs) == 0).mean()):.3f}')
 
 
+def _mtf(things, stuff, thr=0.25, iou=0.5, sma=12, H=24, W=40, seed=0, rand=(0, 0), video=False):
+    """One merge_tf_* case.  things: (rectangles, score, label) per thing in ARRAY order; stuff likewise.  A rectangle is
+    (y0, x0, y1, x1), half-open; `rand` = how many trailing things / stuff masks also get seeded rectangles (synth.rect_masks)."""
+    def table(items):
+        return np.array([(k, *r) for k, (rs, _, _) in enumerate(items) for r in rs], dtype=np.int64).reshape(-1, 5)
+    return dict(case=np.array([H, W, len(things), len(stuff), rand[0], rand[1], seed, int(video)], dtype=np.int64),
+                thing_rects=table(things), stuff_rects=table(stuff),
+                thing_scores=np.array([s for _, s, _ in things], dtype=np.float32), thing_labels=np.array([c for _, _, c in things], dtype=np.int64),
+                stuff_scores=np.array([s for _, s, _ in stuff], dtype=np.float32), stuff_labels=np.array([c for _, _, c in stuff], dtype=np.int64),
+                instance_score_thr=np.float64(thr), iou_thr=np.float64(iou), stuff_max_area=np.int64(sma))
+
+
+def _mtf_edge_things(at_thr, below_thr):
+    """The geometry of merge_tf_edges / merge_tf_thr, in a scrambled array order.  Paste order = descending score:
+    A 8x8 block; B 4 px, 2 of them in A; C 5 px, 3 in A; D 8 px, 5 in A; E empty; F inside A; G a union of two rectangles, clear of
+    everything; H clear, its score ON the threshold; I clear, its score the fp32 value below the threshold; J clear, lower still."""
+    A = ([(0, 0, 8, 8)], 0.95, 0)
+    B = ([(7, 0, 9, 2)], 0.90, 1)
+    C = ([(3, 5, 4, 10)], 0.85, 0)
+    D = ([(5, 3, 6, 11)], 0.80, 0)
+    E = ([], 0.75, 0)
+    Fi = ([(1, 1, 3, 3)], 0.70, 1)
+    G = ([(12, 20, 20, 30), (16, 28, 22, 34)], 0.60, 1)
+    Hh = ([(20, 0, 24, 4)], at_thr, 1)
+    I = ([(0, 30, 4, 36)], below_thr, 1)
+    J = ([(10, 36, 14, 40)], 0.10, 0)
+    return [G, C, A, I, E, B, J, Hh, Fi, D]
+
+
+# stuff of the edge cases (stuff_max_area = 12), paste order s1 .. s5: s1 16 px of which A holds 4 (12 left: ON the limit); s2 12 px of
+# which H holds 1 (11 left); s3 inside A; s4 the whole image; s5 clear of the things, but behind s4
+_MTF_EDGE_STUFF = [([(0, 0, 24, 40)], 0.6, 3), ([(6, 6, 8, 14)], 0.9, 1), ([(10, 10, 14, 14)], 0.5, 5), ([(2, 2, 6, 6)], 0.7, 4),
+                   ([(18, 3, 21, 7)], 0.8, 2)]
+_F32 = np.float32
+MERGE_TF_CASES = {
+    'merge_tf_edges': _mtf(_mtf_edge_things(_F32(0.25), np.nextafter(_F32(0.25), _F32(0))), _MTF_EDGE_STUFF),
+    # thresholds that no fp32 holds: float32(0.3) is above 0.3, float32(0.6) is above 0.6; 3 / 5 in fp64 IS the double 0.6
+    'merge_tf_thr': _mtf(_mtf_edge_things(_F32(0.3), np.nextafter(_F32(0.3), _F32(0))), _MTF_EDGE_STUFF, thr=0.3, iou=0.6),
+    # six stuff masks over three labels; by score the labels run 2 1 2 3 1 3.  Label 2's second mask reaches into label 1's first,
+    # both masks of label 3 lie under the things: with stuff_max_area = 0 that label still becomes a segment, of area 0
+    'merge_tf_dupstuff': _mtf([([(0, 0, 10, 10)], 0.9, 0), ([(4, 4, 14, 14)], 0.8, 1)],
+                              [([(16, 0, 20, 40)], 0.5, 1), ([(0, 20, 6, 30)], 0.9, 2), ([(5, 5, 9, 9)], 0.4, 3), ([(8, 20, 12, 28)], 0.7, 2),
+                               ([(0, 25, 12, 35)], 0.8, 1), ([(1, 1, 4, 4)], 0.6, 3)], sma=0),
+    # scores NOT sorted; thing 2 lies inside thing 1 and is rejected, so the accepted indices are no prefix of the order either
+    'merge_tf_video': _mtf([([(0, 0, 6, 6)], 0.5, 0), ([(10, 10, 20, 24)], 0.9, 1), ([(12, 12, 15, 15)], 0.3, 1), ([(8, 20, 14, 30)], 0.7, 0),
+                            ([], 0.6, 1), ([], 0.8, 0)],
+                           [([(0, 0, 24, 20)], 0.4, 2), ([(0, 20, 24, 40)], 0.6, 1), ([(0, 0, 2, 40)], 0.5, 3)], seed=5, rand=(2, 0), video=True),
+    'merge_tf_empty_things': _mtf([], [([(0, 0, 12, 40)], 0.4, 2), ([(8, 0, 24, 10)], 0.6, 1), ([(0, 0, 3, 3)], 0.5, 3)]),
+    'merge_tf_empty_stuff': _mtf([([(0, 0, 6, 6)], 0.5, 0), ([(3, 3, 20, 24)], 0.9, 1), ([(12, 12, 15, 15)], 0.3, 1)], []),
+    'merge_tf_empty_below': _mtf([([(0, 0, 6, 6)], 0.2, 0), ([(3, 3, 20, 24)], 0.24, 1), ([(12, 12, 15, 15)], 0.1, 1)],
+                                 [([(0, 0, 24, 20)], 0.4, 2), ([(0, 20, 24, 40)], 0.6, 1)]),
+}
+
+
+def run_merge_thing_first(name, p):
+    """`KernelIterHead.merge_stuff_thing` (knet/det/kernel_iter_head.py:386-465) and, for a video case,
+    `VideoKernelIterHead.merge_stuff_thing_thing_first` (knet/video/kernel_iter_head.py:656-741) called DIRECTLY on boolean masks
+    (synth.merge_tf_inputs): stored are the case's parameters and what the reference returned, never the masks."""
+    video = bool(p['case'][7])
+    cfg = head_cfg(video, C=32, heads=8, ffn=64, ncls=5, n_thing=2, n_stuff=3, S=1, up=1, nprop=4)
+    if video:
+        cfg.update(with_track=True, merge_joint=False)
+    else:
+        cfg.update(do_panoptic=True, merge_joint=False)
+    head = build_head(cfg)
+    head.eval()
+    merge_cfg = AttrDict(overlap_thr=0.6, iou_thr=float(p['iou_thr']), stuff_max_area=int(p['stuff_max_area']),
+                         instance_score_thr=float(p['instance_score_thr']))
+    a = {k: torch.from_numpy(v) for k, v in synth.merge_tf_inputs(p).items()}
+    assert len(set(a['thing_scores'].tolist())) == len(a['thing_scores']) and len(set(a['stuff_scores'].tolist())) == len(a['stuff_scores'])
+    args = (a['thing_masks'], a['thing_labels'], a['thing_scores'], a['stuff_masks'], a['stuff_labels'], a['stuff_scores'], merge_cfg)
+    out = dict(p)
+    with torch.no_grad():
+        if video:
+            (pan, info), feats = head.merge_stuff_thing_thing_first(*args, thing_obj_feat=a['thing_obj_feat'])
+            assert feats.shape[1:] == a['thing_obj_feat'].shape[1:]
+            out['feat_rows'] = (feats[:, 0] / 100).round().long().numpy().reshape(-1)        # thing_obj_feat[k, c] = 100 k + c
+            assert torch.equal(feats, a['thing_obj_feat'][torch.from_numpy(out['feat_rows'])])
+        else:
+            pan, info = head.merge_stuff_thing(*args)
+    out['panoptic_seg'] = pan.astype(np.int32)
+    out['info'] = np.array([[s_['id'], int(s_['isthing']), s_['category_id'], s_.get('instance_id', -1), s_.get('score', float('nan')),
+                             s_.get('area', -1)] for s_ in info], dtype=np.float64).reshape(-1, 6)
+    np.savez_compressed(os.path.join(OUT, name + '.npz'), **out)
+    print(f'{name}: ok  segments = {[int(r[0]) for r in out["info"]]}  void = {float((pan == 0).mean()):.3f}')
+
+
 def run_pan_case(name, p):
     """KernelIterHead.get_panoptic of the reference (merge_joint=True) on structured synthetic logits."""
     test_cfg = AttrDict(max_per_img=p['Np'], mask_thr=0.5, stuff_score_thr=0.05,
@@ -724,6 +811,9 @@ if __name__ == '__main__':
     for nm, src in (('pan_tf_tiny', 'pan_tiny'), ('pan_tf_cfg', 'pan_cfg')):
         if not only or nm in only:
             run_pan_thing_first(nm, PAN_CASES[src])
+    for name, p in MERGE_TF_CASES.items():
+        if not only or name in only:
+            run_merge_thing_first(name, p)
     if not only or 'pan_video' in only:
         run_pan_video_case('pan_video', PAN_CASES['pan_tiny'])
     for name, p in ASSIGN_CASES.items():

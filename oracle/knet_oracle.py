@@ -19,6 +19,7 @@ It uses the same ATen op sequence as the reference (1x1 `conv2d`, `sigmoid > thr
 import math
 from dataclasses import dataclass, field
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -407,6 +408,96 @@ def panoptic_joint(cls_scores, mask_logits, num_proposals, num_thing_classes, ma
     return dict(panoptic_seg=panoptic_seg, segments_info=segments_info, cur_mask_ids=cur_mask_ids, total_scores=total_scores,
                 total_labels=total_labels, rows=rows, area=area, orig=orig, seg_of=seg_of, margin=margin,
                 total_masks=total_masks)
+
+
+def thing_first_merge(thing_masks, thing_scores, thing_labels, thing_order, stuff_masks, stuff_labels, stuff_order,
+                      instance_score_thr, iou_thr, stuff_max_area):
+    """The loops of `KernelIterHead.merge_stuff_thing` (knet/det/kernel_iter_head.py:404-464; the video head's
+    `merge_stuff_thing_thing_first`, knet/video/kernel_iter_head.py:677-740, is the same text), with the two paste orders as
+    ARGUMENTS: `thing_order` stands for `sorted_inds` (:403), `stuff_order` lists one mask per distinct label (what :441-451 arrive
+    at; `thing_first_merge_args` below does that part).  Boolean masks [Kt, H, W] / [Ks, H, W] (numpy or torch), fp32 scores.
+    -> dict: panoptic_seg int32 [H, W]; segments_info (the reference's dicts); nseg; info int32 [Kt + Ks, 5], one row per step in
+    paste order, things first: (segment id or 0, kind 0 thing / 1 stuff, label, instance index | stuff: the still-empty area,
+    fp32 score bits | stuff: 0) — the layout of `vkn_panoptic_thing_first_u8` (include/vkn.h), also for rejected steps and for
+    the things behind the `break`."""
+    as_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
+    thing_masks, stuff_masks = as_np(thing_masks).astype(bool), as_np(stuff_masks).astype(bool)
+    thing_scores = as_np(thing_scores).astype(np.float32).reshape(-1)
+    thing_labels, stuff_labels = as_np(thing_labels).reshape(-1), as_np(stuff_labels).reshape(-1)
+    thing_order, stuff_order = [int(k) for k in as_np(thing_order).reshape(-1)], [int(k) for k in as_np(stuff_order).reshape(-1)]
+    H, W = (thing_masks if thing_masks.ndim == 3 and thing_masks.shape[0] else stuff_masks).shape[-2:]
+    panoptic_seg = np.zeros((H, W), dtype=np.int32)                                                   # :396
+    current_segment_id = 0
+    segments_info = []
+    info = np.zeros((len(thing_order) + len(stuff_order), 5), dtype=np.int32)
+    broke = False
+    for step, inst_id in enumerate(thing_order):                                                      # :407
+        bits = int(thing_scores[inst_id:inst_id + 1].view(np.int32)[0])
+        info[step] = (0, 0, int(thing_labels[inst_id]), inst_id, bits)
+        if broke:
+            continue
+        score = float(thing_scores[inst_id])                                                          # `.item()`: the fp32 value as a double
+        if score < instance_score_thr:                                                                # :409-410
+            broke = True
+            continue
+        mask = thing_masks[inst_id]
+        mask_area = int(mask.sum())
+        if mask_area == 0:                                                                            # :414
+            continue
+        intersect_area = int((mask & (panoptic_seg > 0)).sum())                                       # :417-418
+        if intersect_area * 1.0 / mask_area > iou_thr:                                                # :420
+            continue
+        if intersect_area > 0:
+            mask = mask & (panoptic_seg == 0)                                                         # :424
+        mask_area = int(mask.sum())
+        if mask_area == 0:                                                                            # :427
+            continue
+        current_segment_id += 1
+        panoptic_seg[mask] = current_segment_id
+        segments_info.append(dict(id=current_segment_id, isthing=True, score=score, category_id=int(thing_labels[inst_id]),
+                                  instance_id=inst_id))
+        info[step, 0] = current_segment_id
+    for step, k in enumerate(stuff_order, start=len(thing_order)):                                    # :445
+        mask = stuff_masks[k] & (panoptic_seg == 0)                                                   # :452
+        mask_area = int(mask.sum())
+        info[step] = (0, 1, int(stuff_labels[k]), mask_area, 0)
+        if mask_area < stuff_max_area:                                                                # :454
+            continue
+        current_segment_id += 1
+        panoptic_seg[mask] = current_segment_id
+        segments_info.append(dict(id=current_segment_id, isthing=False, category_id=int(stuff_labels[k]), area=mask_area))
+        info[step, 0] = current_segment_id
+    return dict(panoptic_seg=panoptic_seg, segments_info=segments_info, nseg=current_segment_id, info=info)
+
+
+def thing_first_merge_args(thing_masks, thing_labels, thing_scores, stuff_masks, stuff_labels, stuff_scores):
+    """What `merge_stuff_thing` does around its loops, from the head-level arguments to those of `thing_first_merge`: things in
+    `argsort(-thing_scores)` order (:403); stuff labels walked in `argsort(-stuff_scores)` order, every label once, at its FIRST
+    occurrence, with the OR of all the masks that carry it (:441-451).  Scores must be distinct (torch.argsort is not stable).
+    -> the seven leading arguments of `thing_first_merge`, as a dict."""
+    as_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
+    thing_scores, stuff_scores = as_np(thing_scores).astype(np.float32), as_np(stuff_scores).astype(np.float32)
+    assert len(set(thing_scores.tolist())) == thing_scores.size and len(set(stuff_scores.tolist())) == stuff_scores.size
+    stuff_masks, stuff_labels = as_np(stuff_masks).astype(bool), as_np(stuff_labels)
+    sorted_inds = np.argsort(-stuff_scores, kind='stable')
+    processed_label, merged = [], []
+    for semantic_label in stuff_labels[sorted_inds].tolist():
+        if semantic_label in processed_label:
+            continue
+        processed_label.append(semantic_label)
+        merged.append(stuff_masks[stuff_labels == semantic_label].sum(0).astype(bool))
+    merged = np.stack(merged) if merged else np.zeros((0,) + stuff_masks.shape[1:], dtype=bool)
+    return dict(thing_masks=as_np(thing_masks).astype(bool), thing_scores=thing_scores, thing_labels=as_np(thing_labels),
+                thing_order=np.argsort(-thing_scores, kind='stable'), stuff_masks=merged,
+                stuff_labels=np.asarray(processed_label, dtype=np.int64), stuff_order=np.arange(len(processed_label)))
+
+
+def thing_first_feat_rows(thing_order, segments_info):
+    """The rows of `thing_obj_feat` behind what `merge_stuff_thing_thing_first` returns: the reference sorts the embeddings by
+    score first (`thing_obj_feat[sorted_inds]`, knet/video/kernel_iter_head.py:676) and then indexes the SORTED array with the
+    accepted things' positions in the UNSORTED one (`[instance_ids]`, :741) — row `sorted_inds[instance_id]` per accepted thing."""
+    order = np.asarray(thing_order).reshape(-1)
+    return np.array([int(order[s['instance_id']]) for s in segments_info if s['isthing']], dtype=np.int64)
 
 
 def assign_costs(mask_preds, cls_pred, gt_masks, gt_labels, cls_weight=2.0, dice_weight=4.0, mask_weight=1.0,

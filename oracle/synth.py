@@ -97,6 +97,52 @@ def panoptic_inputs(B, N, Np, ncls, Hm, Wm, seed):
     return cls.astype(np.float32), (logits + noise).astype(np.float32)
 
 
+def random_rects(K, H, W, seed, per_mask=2):
+    """A rectangle table [K * per_mask, 5] of rows (mask, y0, x0, y1, x1), half-open, every rectangle non-empty and inside H x W:
+    corner and extent from the hash of (seed, row), extents up to half of each side."""
+    n = K * per_mask
+    u = uniform((n, 4), 7300 + 31 * seed, 0.0, 1.0).astype(np.float64)
+    hh = 1 + (u[:, 0] * max(H // 2, 1)).astype(np.int64)
+    ww = 1 + (u[:, 1] * max(W // 2, 1)).astype(np.int64)
+    hh, ww = np.minimum(hh, H), np.minimum(ww, W)
+    y0 = (u[:, 2] * (H - hh + 1)).astype(np.int64)
+    x0 = (u[:, 3] * (W - ww + 1)).astype(np.int64)
+    return np.stack([np.arange(n, dtype=np.int64) // per_mask, y0, x0, y0 + hh, x0 + ww], 1)
+
+
+def rect_masks(K, H, W, rects, n_rand=0, seed=0):
+    """Boolean masks [K, H, W] for the merge tests: mask k is the UNION of the rectangles [y0, y1) x [x0, x1) that the rows
+    (k, y0, x0, y1, x1) of `rects` list (no row: an empty mask), so that areas and overlaps are what the table says, pixel for pixel.
+    The LAST `n_rand` masks get, on top of their rows, the two hashed rectangles `random_rects(n_rand, H, W, seed)` gives them."""
+    masks = np.zeros((K, H, W), dtype=bool)
+    table = np.asarray(rects, dtype=np.int64).reshape(-1, 5)
+    if n_rand:
+        extra = random_rects(n_rand, H, W, seed)
+        extra[:, 0] += K - n_rand
+        table = np.concatenate([table, extra])
+    for k, y0, x0, y1, x1 in table.tolist():
+        assert 0 <= k < K and 0 <= y0 <= y1 <= H and 0 <= x0 <= x1 <= W, (k, y0, x0, y1, x1)
+        masks[k, y0:y1, x0:x1] = True
+    return masks
+
+
+MERGE_TF_FIELDS = ('H', 'W', 'Kt', 'Ks', 'rand_t', 'rand_s', 'seed', 'video')
+
+
+def merge_tf_inputs(p):
+    """The head-level arguments of a thing-first merge case (tests/golden/merge_tf_*.npz, or the generator's parameter dict) rebuilt
+    from its parameters: boolean masks from the rectangle tables, scores and labels as stored, and for a video case embeddings whose
+    rows can be told apart (`thing_obj_feat[k, c] = 100 k + c`)."""
+    c = dict(zip(MERGE_TF_FIELDS, (int(v) for v in p['case'])))
+    out = dict(thing_masks=rect_masks(c['Kt'], c['H'], c['W'], p['thing_rects'], c['rand_t'], c['seed']),
+               stuff_masks=rect_masks(c['Ks'], c['H'], c['W'], p['stuff_rects'], c['rand_s'], c['seed'] + 1),
+               thing_scores=np.asarray(p['thing_scores'], dtype=np.float32), thing_labels=np.asarray(p['thing_labels'], dtype=np.int64),
+               stuff_scores=np.asarray(p['stuff_scores'], dtype=np.float32), stuff_labels=np.asarray(p['stuff_labels'], dtype=np.int64))
+    if c['video']:
+        out['thing_obj_feat'] = (100.0 * np.arange(c['Kt'])[:, None] + np.arange(8)[None, :]).astype(np.float32)
+    return out
+
+
 def assign_inputs(N, G, ncls, H, W, seed):
     """Inputs of the train-time assignment for one image: mask logits [N,H,W] (blobs + noise), class logits [N,ncls],
     ground-truth masks [G,H,W] in {0,1} (G of the blobs, thresholded, so that a good matching exists) and labels [G]."""

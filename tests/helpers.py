@@ -122,6 +122,25 @@ def pan_info_rows(segments_info):
                       s.get('area', -1)] for s in segments_info], dtype=np.float64).reshape(-1, 6)
 
 
+MERGE_TF = ('merge_tf_edges', 'merge_tf_thr', 'merge_tf_dupstuff', 'merge_tf_video', 'merge_tf_empty_things', 'merge_tf_empty_stuff',
+            'merge_tf_empty_below')
+
+
+def load_merge_tf(name):
+    """A thing-first merge fixture -> (golden, head-level inputs rebuilt from its parameters (numpy), merge thresholds)."""
+    g = dict(np.load(os.path.join(GOLDEN, name + '.npz'), allow_pickle=False))
+    thr = dict(instance_score_thr=float(g['instance_score_thr']), iou_thr=float(g['iou_thr']), stuff_max_area=int(g['stuff_max_area']))
+    return g, synth.merge_tf_inputs(g), thr
+
+
+def merge_tf_oracle(a, thr):
+    """oracle.thing_first_merge on head-level inputs `a` -> (its ABI-level arguments, its result)."""
+    from oracle.knet_oracle import thing_first_merge, thing_first_merge_args
+    args = thing_first_merge_args(a['thing_masks'], a['thing_labels'], a['thing_scores'], a['stuff_masks'], a['stuff_labels'],
+                                  a['stuff_scores'])
+    return args, thing_first_merge(**args, **thr)
+
+
 ASSIGN_FIELDS = ('N', 'G', 'ncls', 'H', 'W', 'seed')
 
 

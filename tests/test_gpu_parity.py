@@ -877,8 +877,11 @@ def test_video_simple_test_with_previous(vkn):
 def test_thing_first_merge_vs_reference_golden(vkn, name):
     """merge_joint=False: `get_panoptic` -> `merge_stuff_thing` (knet/det/kernel_iter_head.py:385-465) on the device: segment list
     (ids, kinds, labels, instance indices, scores) equal, stuff areas and the map equal up to the few pixels whose rescaled
-    probability sits on the 0.5 threshold."""
+    probability sits on the 0.5 threshold.  That slack is the fp32 rescale's alone: on the boolean masks the head itself thresholds
+    (recomputed here: same top-k, same stuff order, same `rescale_masks(...) > mask_thr`) the merge has one right answer,
+    `oracle.thing_first_merge`, and the head's map and segment table equal it exactly."""
     from helpers import load_pan_golden, make_pan_case, pan_info_rows
+    from oracle.knet_oracle import thing_first_merge, thing_first_merge_args
     g, case = load_pan_golden(name)
     cls, logits, meta = make_pan_case(case)
     cfg = vkn.configs.roi_head_cfg(False, C=32, heads=8, ffn=64, ncls=case['ncls'], n_thing=case['T'], n_stuff=case['ncls'] - case['T'],
@@ -896,6 +899,17 @@ def test_thing_first_merge_vs_reference_golden(vkn, name):
         assert np.all(np.abs(rows[stuff, 5] - ref[stuff, 5]) <= 0.002 * ref[stuff, 5] + 8)
         assert np.mean(seg != g['panoptic_seg'][b]) < 2e-3
         assert sum(len(m) for m in segm_result) == int(g[f'nmask{b}'])
+        # the merge alone, exact
+        Np, T, last = case['Np'], case['T'], head.mask_head[-1]
+        c, m = cls[b].to(DEV), scaled[b].to(DEV)
+        thing_scores, topk = c[:Np][:, :T].flatten(0, 1).topk(case['Np'], sorted=True)
+        thing_masks = last.rescale_masks(m[:Np][topk // T], meta) > 0.5
+        stuff_scores, stuff_inds = torch.sort(c[Np:][:, T:].diag(), descending=True)
+        stuff_masks = last.rescale_masks(m[Np:][stuff_inds], meta) > 0.5
+        r = thing_first_merge(**thing_first_merge_args(thing_masks, topk % T, thing_scores, stuff_masks, stuff_inds + 1, stuff_scores),
+                              instance_score_thr=0.25, iou_thr=0.5, stuff_max_area=int(g['stuff_max_area']))
+        assert np.array_equal(seg, r['panoptic_seg'])
+        assert np.array_equal(rows, pan_info_rows(r['segments_info']), equal_nan=True)
 
 
 def test_instance_only_results_vs_reference_golden(vkn):

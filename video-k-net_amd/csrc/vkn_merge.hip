@@ -91,7 +91,8 @@ int vkn_panoptic_thing_first_u8(const unsigned char* thing_masks, const float* t
                                 const int* stuff_order, int Ks, int HW, double instance_score_thr, double iou_thr,
                                 int stuff_max_area, int* panoptic_seg, int* info, int* nseg, void* ws, size_t ws_bytes,
                                 void* stream) {
-    if (Kt < 0 || Ks < 0 || HW <= 0 || !panoptic_seg || !info || !nseg) return VKN_E_ARG;
+    if (Kt < 0 || Ks < 0 || HW <= 0 || !panoptic_seg || !nseg) return VKN_E_ARG;
+    if (Kt + Ks > 0 && !info) return VKN_E_ARG;                                            // no step, no row: a [0][5] table has no address
     if (Kt > 0 && (!thing_masks || !thing_scores || !thing_labels || !thing_order)) return VKN_E_ARG;
     if (Ks > 0 && (!stuff_masks || !stuff_labels || !stuff_order)) return VKN_E_ARG;
     if (!ws || ws_bytes < vkn_merge_workspace_bytes(Kt, Ks)) return VKN_E_WORKSPACE;
