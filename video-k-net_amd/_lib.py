@@ -12,8 +12,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libvkn.so')
-SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_api.hip')
+SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_api.hip')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn.h')
+TRACK_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_track.h')     # second part of the ABI: the tracking tail
 
 
 class VknLibraryError(RuntimeError):
@@ -91,6 +92,12 @@ def read_header(text):
 with open(HEADER) as _f:
     PROTOS, STRUCTS, CONSTS = read_header(_f.read())
 SYMBOLS = tuple(PROTOS)                     # every symbol include/vkn.h declares
+with open(HEADER) as _f, open(TRACK_HEADER) as _g:          # vkn_track.h builds on vkn.h's structs: read behind it, keep what it adds
+    _protos, _, _consts = read_header(_f.read() + '\n' + _g.read())
+TRACK_PROTOS = {k: v for k, v in _protos.items() if k not in PROTOS}
+TRACK_SYMBOLS = tuple(TRACK_PROTOS)         # every symbol include/vkn_track.h declares
+CONSTS.update({k: v for k, v in _consts.items() if k not in CONSTS})
+TRACK_MAX_K = CONSTS['VKN_TRACK_MAX_K']
 MAX_FCS = CONSTS['VKN_MAX_FCS']
 SPLIT_MAX_ITEMS = CONSTS['VKN_SPLIT_MAX_ITEMS']
 DW_MAX_ITEMS = CONSTS['VKN_DW_MAX_ITEMS']
@@ -145,7 +152,7 @@ def _hipcc(args, verbose=False, what='hipcc'):
 def _shared_deps(debug):
     """What every object depends on besides csrc/: the public header and, in the debug build, the kernel variants it #includes."""
     exp = os.path.join(os.path.dirname(HERE), 'tools', 'experiments')
-    return [HEADER] + ([os.path.join(exp, f) for f in os.listdir(exp)] if debug and os.path.isdir(exp) else [])
+    return [HEADER, TRACK_HEADER] + ([os.path.join(exp, f) for f in os.listdir(exp)] if debug and os.path.isdir(exp) else [])
 
 
 def _stale(path=None):
@@ -222,7 +229,7 @@ def lib():
         raise VknLibraryError(f'{path} is missing — run `python -c "import __graft_entry__ as g; g.build()"` '
                               '(there is deliberately no CPU fallback)')
     L = ctypes.CDLL(path)
-    for name, (result, params) in PROTOS.items():
+    for name, (result, params) in {**PROTOS, **TRACK_PROTOS}.items():
         fn = getattr(L, name)
         fn.restype = _ctype(*result, name, result=True)
         fn.argtypes = [POINTER_EXCEPTIONS.get((name, p)) or _ctype(base, depth, name) for p, base, depth in params]

@@ -22,6 +22,7 @@
 // Floating-point contraction is OFF in this file: every value that feeds a decision is computed with the same sequence of
 // individually rounded fp32 operations as the reference's element-wise tensor ops (IoU, momentum update, softmax division).
 #include "../../include/vkn.h"
+#include "../../include/vkn_track.h"
 #include "vkn_common.h"
 
 #pragma clang fp contract(off)
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(TRK_THREADS) void k_qd_match(VknTrackerCfg cfg, cha
                                                             const long long* __restrict__ labels, const float* __restrict__ embeds,
                                                             int n, int frame_id, float* __restrict__ out_boxes,
                                                             long long* __restrict__ out_labels, long long* __restrict__ out_ids,
-                                                            int* __restrict__ out_count, char* wsbuf) {
+                                                            int* __restrict__ out_count, char* wsbuf, const int* __restrict__ n_dev) {
     __shared__ float s_score[TRK_MAX_D];
     __shared__ int s_order[TRK_MAX_D];         // sorted position -> input row
     __shared__ float s_box[TRK_MAX_D][5];      // sorted boxes
@@ -138,6 +139,17 @@ __global__ __launch_bounds__(TRK_THREADS) void k_qd_match(VknTrackerCfg cfg, cha
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int D = cfg.max_dets, E = cfg.embed_dim, T = cfg.max_tracklets, F = trk_frames(cfg);
+    if (n_dev) {   // vkn_qd_tracker_match_dev_f32: the count lives on the device; `n` is the capacity of the input rows
+        const int nd = *n_dev;
+        n = nd < n ? nd : n;
+        if (n <= 0) {   // a frame without detections is not a tracker call: the state stays as it is
+            if (tid == 0) {
+                out_count[0] = 0;
+                out_count[1] = 0;
+            }
+            return;
+        }
+    }
     TrkState st;
     TrkWs ws;
     trk_carve(cfg, state, &st);
@@ -573,7 +585,26 @@ int vkn_qd_tracker_match_f32(const VknTrackerCfg* cfg, void* state, size_t state
     hipLaunchKernelGGL(k_qd_match, dim3(1), dim3(TRK_THREADS), 0, static_cast<hipStream_t>(stream), *cfg, static_cast<char*>(state),
                        bboxes, reinterpret_cast<const long long*>(labels), embeds, n, frame_id, out_bboxes,
                        reinterpret_cast<long long*>(out_labels), reinterpret_cast<long long*>(out_ids), out_count,
-                       static_cast<char*>(ws));
+                       static_cast<char*>(ws), static_cast<const int*>(nullptr));
+    VKN_CHECK_LAUNCH();
+    return VKN_OK;
+}
+
+int vkn_qd_tracker_match_dev_f32(const VknTrackerCfg* cfg, void* state, size_t state_bytes, const float* bboxes, const int64_t* labels,
+                                 const float* embeds, const int* n_dev, int n_max, int frame_id, float* out_bboxes, int64_t* out_labels,
+                                 int64_t* out_ids, int* out_count, void* ws, size_t ws_bytes, void* stream) {
+    const int rc = trk_check(cfg);
+    if (rc != VKN_OK) return rc;
+    if (!state || !out_count || !n_dev || n_max <= 0) return VKN_E_ARG;
+    if (!bboxes || !labels || !embeds || !out_bboxes || !out_labels || !out_ids) return VKN_E_ARG;
+    if (n_max > cfg->max_dets) return VKN_E_SHAPE;
+    if (state_bytes < vkn_qd_tracker_state_bytes(cfg)) return VKN_E_WORKSPACE;
+    if (!ws || ws_bytes < vkn_qd_tracker_workspace_bytes(cfg)) return VKN_E_WORKSPACE;
+    if ((reinterpret_cast<uintptr_t>(state) & 255) || (reinterpret_cast<uintptr_t>(ws) & 255)) return VKN_E_ALIGN;
+    hipLaunchKernelGGL(k_qd_match, dim3(1), dim3(TRK_THREADS), 0, static_cast<hipStream_t>(stream), *cfg, static_cast<char*>(state),
+                       bboxes, reinterpret_cast<const long long*>(labels), embeds, n_max, frame_id, out_bboxes,
+                       reinterpret_cast<long long*>(out_labels), reinterpret_cast<long long*>(out_ids), out_count,
+                       static_cast<char*>(ws), n_dev);
     VKN_CHECK_LAUNCH();
     return VKN_OK;
 }

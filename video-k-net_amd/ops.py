@@ -689,6 +689,74 @@ def panoptic_joint(cls_prob, mask_logits, num_proposals, num_thing_classes, max_
     return (seg, info, nseg, bbox) if want_bbox else (seg, info, nseg)
 
 
+def _req_int(t, name, dtype=torch.int32):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.VknLibraryError(f'{name}: expected a CUDA/HIP tensor — the MI355X path has no CPU fallback')
+    if t.dtype != dtype:
+        raise TypeError(f'{name}: expected {dtype}, got {t.dtype}')
+    t = t.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
+def track_boxes(panoptic_seg, info, nseg, num_thing_classes, sem_logits=None, want_thing_mask=False):
+    """What the video detector hands its tracker, for the frames [B] of one geometry, straight from `panoptic_joint`'s outputs
+    (`get_things_id_for_tracking` + the semantic filter + `tensor_mask2box`, knet/video/knet_quansi_dense_embed_fc_joint_train.py:
+    541-584, 673-685).  `sem_logits` [B,Cs,hs,ws] fp32 (the kernel-init head's `seg_preds`) switches the semantic filter on.
+    Returns device tensors (det fp32 [B,K,5], labels int64 [B,K], rows int32 [B,K], segid int32 [B,K], count int32 [B]) and, with
+    `want_thing_mask`, a sixth one: thing_mask uint8 [B,Ho,Wo]; see include/vkn_track.h."""
+    seg, inf, ns = _req_int(panoptic_seg, 'panoptic_seg'), _req_int(info, 'info'), _req_int(nseg, 'nseg')
+    if seg.dim() != 3 or inf.dim() != 3 or inf.shape[0] != seg.shape[0] or inf.shape[2] != 6 or ns.numel() != seg.shape[0]:
+        raise ValueError('panoptic_seg [B,Ho,Wo], info [B,K,6] and nseg [B] disagree')
+    B, Ho, Wo = (int(v) for v in seg.shape)
+    K = int(inf.shape[1])
+    Cs = hs = ws_w = 0
+    sem = None
+    if sem_logits is not None:
+        sem = _req(sem_logits, 'sem_logits')
+        if sem.dim() != 4 or sem.shape[0] != B:
+            raise ValueError('sem_logits must be [B,Cs,hs,ws]')
+        Cs, hs, ws_w = (int(v) for v in sem.shape[1:])
+    dev = seg.device
+    L = _lib.lib()
+    det = torch.empty((B, K, 5), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, K), dtype=torch.int64, device=dev)
+    rows = torch.empty((B, K), dtype=torch.int32, device=dev)
+    segid = torch.empty((B, K), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    tmask = torch.empty((B, Ho, Wo), dtype=torch.uint8, device=dev) if want_thing_mask else None
+    ws = _workspace(max(L.vkn_track_boxes_workspace_bytes(B, K), 256), dev, scratch=True)
+    with torch.cuda.device(dev):
+        check(L.vkn_track_boxes_f32(_ptr(seg), _ptr(inf), _ptr(ns), _ptr(sem), Cs, hs, ws_w, int(num_thing_classes), B, K, Ho, Wo,
+                                    _ptr(det), _ptr(labels), _ptr(rows), _ptr(segid), _ptr(count), _ptr(tmask), _ptr(ws), ws.numel(),
+                                    _stream()))
+    return (det, labels, rows, segid, count, tmask) if want_thing_mask else (det, labels, rows, segid, count)
+
+
+def track_maps(panoptic_seg, segid, count, ids, n_ids, info, sem_of_label):
+    """The two maps the video detector returns (`generate_track_id_maps` + `get_semantic_seg`,
+    knet/video/knet_quansi_dense_embed_fc_joint_train.py:591-592, 698-736) as int32 device tensors [B,Ho,Wo]:
+    (track_map, semantic_map).  `ids` int64 [B,max_dets] / `n_ids` int32 [B] are the tracker's padded outputs, `segid` / `count` those of
+    `track_boxes`, `sem_of_label` int32 [num_thing_classes + num_stuff_classes] a device table; see include/vkn_track.h."""
+    seg, inf = _req_int(panoptic_seg, 'panoptic_seg'), _req_int(info, 'info')
+    sg, ct = _req_int(segid, 'segid'), _req_int(count, 'count')
+    ii, ni, tab = _req_int(ids, 'ids', torch.int64), _req_int(n_ids, 'n_ids'), _req_int(sem_of_label, 'sem_of_label')
+    B, Ho, Wo = (int(v) for v in seg.shape)
+    K = int(inf.shape[1])
+    if sg.shape != (B, K) or ct.numel() != B or ii.dim() != 2 or ii.shape[0] != B or ni.numel() != B or inf.shape[0] != B:
+        raise ValueError('segid [B,K], count [B], ids [B,max_dets], n_ids [B] and info [B,K,6] disagree')
+    dev = seg.device
+    L = _lib.lib()
+    track_map = torch.empty((B, Ho, Wo), dtype=torch.int32, device=dev)
+    semantic_map = torch.empty((B, Ho, Wo), dtype=torch.int32, device=dev)
+    ws = _workspace(max(L.vkn_track_maps_workspace_bytes(B, K), 256), dev, scratch=True)
+    with torch.cuda.device(dev):
+        check(L.vkn_track_maps_i32(_ptr(seg), _ptr(sg), _ptr(ct), _ptr(ii), _ptr(ni), int(ii.shape[1]), _ptr(inf), _ptr(tab),
+                                   int(tab.numel()), B, K, Ho, Wo, _ptr(track_map), _ptr(semantic_map), _ptr(ws), ws.numel(), _stream()))
+    return track_map, semantic_map
+
+
 def panoptic_thing_first(thing_masks, thing_scores, thing_labels, thing_order, stuff_masks, stuff_labels, stuff_order,
                          instance_score_thr, iou_thr, stuff_max_area):
     """Thing-first panoptic merge of ONE image on the device (`merge_stuff_thing`, knet/det/kernel_iter_head.py:385-465).

@@ -82,16 +82,23 @@ class QuasiDenseEmbedTracker:
         self._cfg = self._state = self._ws = self._layout = self._device = None
 
     # ------------------------------------------------------------------ the per-frame call
-    def match_padded(self, bboxes, labels, track_feats, frame_id):
+    def match_padded(self, bboxes, labels, track_feats, frame_id, count=None):
         """-> (out_bboxes [max_dets,5], out_labels [max_dets], out_ids [max_dets] int64, count int32 [2] = (survivors, status)),
-        all on the device, nothing synchronised: rows [0, count[0]) are the surviving detections in score order."""
-        if not (torch.is_tensor(bboxes) and bboxes.is_cuda and labels.is_cuda and track_feats.is_cuda):
+        all on the device, nothing synchronised: rows [0, count[0]) are the surviving detections in score order.
+        `count` (int32 device tensor [1]) puts the number of detections on the DEVICE (`vkn_qd_tracker_match_dev_f32`): the inputs
+        hold `bboxes.shape[0]` >= 1 rows of which the first min(count, rows) are detections; count == 0 is not a tracker call — the
+        state stays as it is and the returned count is 0 (the detector skips its tracker for a frame without things, reference
+        :569-573)."""
+        tensors = (bboxes, labels, track_feats) + (() if count is None else (count,))
+        if not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
             raise _lib.VknLibraryError('QuasiDenseEmbedTracker: expected CUDA/HIP tensors — the MI355X path has no CPU fallback')
         n = int(bboxes.shape[0])
         if bboxes.dim() != 2 or bboxes.shape[1] != 5 or labels.shape[0] != n or track_feats.shape[0] != n:
             raise ValueError('bboxes [n,5] (x1, y1, x2, y2, score), labels [n], track_feats [n,E]')
         if n > self.max_dets:
             raise ValueError(f'{n} detections > max_dets = {self.max_dets}')
+        if count is not None and n < 1:
+            raise ValueError('a device-side count needs at least one input row')
         dev = bboxes.device
         self._ensure(dev, int(track_feats.shape[1]))
         bb = bboxes.detach().to(torch.float32).contiguous()
@@ -102,11 +109,15 @@ class QuasiDenseEmbedTracker:
         out_l = torch.empty((D,), dtype=torch.int64, device=dev)
         tail = torch.empty((D + 1,), dtype=torch.int64, device=dev)      # ids [D] | (count, status) as two int32
         L = _lib.lib()
+        head = (ctypes.byref(self._cfg), ops._ptr(self._state), self._state.numel(), ops._ptr(bb), ops._ptr(lb), ops._ptr(em))
+        rest = (int(frame_id), ops._ptr(out_b), ops._ptr(out_l), ops._ptr(tail), ctypes.c_void_p(tail.data_ptr() + 8 * D),
+                ops._ptr(self._ws), self._ws.numel(), ops._stream())
         with torch.cuda.device(dev):
-            _lib.check(L.vkn_qd_tracker_match_f32(ctypes.byref(self._cfg), ops._ptr(self._state), self._state.numel(), ops._ptr(bb),
-                                                  ops._ptr(lb), ops._ptr(em), n, int(frame_id), ops._ptr(out_b), ops._ptr(out_l),
-                                                  ops._ptr(tail), ctypes.c_void_p(tail.data_ptr() + 8 * D), ops._ptr(self._ws),
-                                                  self._ws.numel(), ops._stream()))
+            if count is None:
+                _lib.check(L.vkn_qd_tracker_match_f32(*head, n, *rest))
+            else:
+                ct = count.detach().to(torch.int32).contiguous()
+                _lib.check(L.vkn_qd_tracker_match_dev_f32(*head, ops._ptr(ct), n, *rest))
         self._tail = tail
         return out_b, out_l, tail[:D], tail[D:].view(torch.int32)
 
