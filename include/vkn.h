@@ -792,7 +792,10 @@ int vkn_sum_n_f32(const float* const* srcs, int nsrc, size_t n, float* out, void
  *           out_count[0] = number of surviving detections, out_count[1] = status bits OF THIS CALL (1: tracklet table full, a birth
  *           was dropped — its id is still consumed); the state header keeps the union over all calls since the reset.
  *      Equal scores are ordered by input row (torch's unstable sort leaves that order unspecified).  memo_keep = float(1.0 -
- *      double(memo_momentum)): Python evaluates `1 - self.memo_momentum` in double before it meets the fp32 tensor. */
+ *      double(memo_momentum)): Python evaluates `1 - self.memo_momentum` in double before it meets the fp32 tensor.
+ *      Envelope: max_dets <= 256, max_tracklets + max(memo_backdrop_frames, 1) * max_dets <= 4096, embed_dim <= 1024,
+ *      memo_backdrop_frames <= 64 (VKN_TRACKER_MAX_BACKDROP_FRAMES, vkn_track.h); outside it the size queries answer 0 and every entry
+ *      returns VKN_E_SHAPE before a launch.  Full table: see vkn_track.h. */
 typedef struct VknTrackerCfg {
     float init_score_thr, obj_score_thr, match_score_thr;
     float memo_momentum, memo_keep;

@@ -66,6 +66,15 @@ int vkn_track_maps_i32(const int* panoptic_seg, const int* segid, const int* cou
                        const int* info, const int* sem_of_label, int num_labels, int B, int K, int Ho, int Wo, int* track_map,
                        int* semantic_map, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the tracker's envelope (vkn_qd_tracker_* of vkn.h and the entry below): max_dets <= 256, max_tracklets +
+ *      max(memo_backdrop_frames, 1) * max_dets <= 4096, embed_dim <= 1024 and memo_backdrop_frames <= VKN_TRACKER_MAX_BACKDROP_FRAMES
+ *      (the match kernel keeps one offset per backdrop frame in LDS).  Outside it vkn_qd_tracker_state_bytes / _workspace_bytes answer
+ *      0 and _state_layout, _reset, _match_f32 and _match_dev_f32 return VKN_E_SHAPE before any launch.
+ *      Full tracklet table: a birth that finds max_tracklets live rows is dropped (status bit 1 of that call; its id is consumed and
+ *      returned).  The capacity test runs BEFORE the expiry compaction of the same call, so a birth into a full table is dropped
+ *      even when another track expires in that very frame; the freed row serves the next frame. */
+#define VKN_TRACKER_MAX_BACKDROP_FRAMES 64
+
 /* ---- vkn_qd_tracker_match_f32 (vkn.h) with the number of detections in DEVICE memory: n = min(*n_dev, n_max), where n_max <=
  *      cfg->max_dets is the number of rows the input buffers hold (count / K of vkn_track_boxes_f32).  n == 0 — a frame without
  *      things, which the detector does not hand to its tracker (:569-573, :597-598) — writes out_count = (0, 0) and leaves the state

@@ -77,11 +77,57 @@ CFG = dict(init_score_thr=0.35, obj_score_thr=0.3, match_score_thr=0.5, memo_tra
            memo_momentum=0.8, nms_conf_thr=0.5, nms_backdrop_iou_thr=0.3, nms_class_iou_thr=0.7, with_cats=True,
            match_metric='bisoftmax')      # configs/det/video_knet_vipseg/..._joint_train_8e.py: tracker=dict(...)
 
+# ---- the configuration axes qd_tracker.npz does not visit (tests/golden/qd_tracker_edges.npz): name -> (T, n_obj, emb, n_cls, seed,
+#      frame ids, overrides of CFG)
+EDGE_VIDEOS = dict(
+    edge_nocats=(8, 14, 16, 3, 11, list(range(8)), dict(with_cats=False)),
+    edge_mom03=(8, 14, 16, 2, 12, list(range(8)), dict(memo_momentum=0.3, match_metric='softmax')),
+    edge_bd3=(10, 24, 16, 3, 13, list(range(10)), dict(memo_backdrop_frames=3)),
+    edge_all_gaps=(8, 18, 16, 2, 14, [0, 1, 4, 5, 6, 9, 10, 12], dict(with_cats=False, memo_momentum=0.3, memo_backdrop_frames=3,
+                                                                      match_metric='cosine')))
+
+
+def write_edges(Tracker, path):
+    """The four videos above and the hand-made cases of tests/tracker_edge_cases.py (those without equal scores: the reference's sort
+    leaves their order open) through the reference's own class; data only: parameters, ids, labels, boxes."""
+    import json
+    sys.path.insert(2, os.path.join(ROOT, 'tests'))
+    import tracker_edge_cases as TC
+    out = dict(video_names=np.array(sorted(EDGE_VIDEOS)))
+    for name, (T, n_obj, emb, n_cls, seed, fids, over) in EDGE_VIDEOS.items():
+        trk = Tracker(**dict(CFG, **over))
+        out[name + '_case'] = np.array([T, n_obj, emb, n_cls, seed], dtype=np.int64)
+        out[name + '_frame_ids'] = np.array(fids, dtype=np.int64)
+        out[name + '_cfg'] = np.array(json.dumps(dict(CFG, **over), sort_keys=True))
+        for t, (bb, lab, em, _) in enumerate(synth.tracker_sequence(T, n_obj, emb, n_cls, seed)):
+            b, l_, ids = trk.match(bboxes=torch.from_numpy(bb), labels=torch.from_numpy(lab), track_feats=torch.from_numpy(em), frame_id=fids[t])
+            out[f'{name}_bboxes{t}'], out[f'{name}_labels{t}'], out[f'{name}_ids{t}'] = b.numpy(), l_.numpy(), ids.numpy()
+        print(name, 'ok  tracklets created:', int(trk.num_tracklets), ' last frame ids:', ids.tolist())
+    names = [n for n, c in TC.CASES.items() if c['reference']]
+    out['case_names'] = np.array(names)
+    for n in names:
+        c = TC.CASES[n]
+        trk = Tracker(**c['cfg'])
+        for t, (fid, bb, lab, em) in enumerate(TC.inputs(c)):
+            b, l_, ids = trk.match(bboxes=torch.from_numpy(bb), labels=torch.from_numpy(lab), track_feats=torch.from_numpy(em), frame_id=fid)
+            out[f'case_{n}_bboxes{t}'], out[f'case_{n}_labels{t}'], out[f'case_{n}_ids{t}'] = b.numpy(), l_.numpy(), ids.numpy()
+    print(len(names), 'hand-made cases ok')
+    np.savez_compressed(path, **out)
+
+
 if __name__ == '__main__':
+    # `gen_golden_tracker.py [tracker] [edges] [embed]`: the outputs to write (default: all three).  A re-written .npz differs in its
+    # zip time stamps, so write only the file that is meant to change.
+    which = set(sys.argv[1:]) or {'tracker', 'edges', 'embed'}
+    assert which <= {'tracker', 'edges', 'embed'}, which
+    GOLDEN_OUT = os.environ.get('VKN_GOLDEN_OUT', os.path.join(ROOT, 'tests', 'golden'))
     Tracker = load_reference_tracker()
+    if 'edges' in which:
+        write_edges(Tracker, os.path.join(GOLDEN_OUT, 'qd_tracker_edges.npz'))
     out = dict()
     for name, (T, n_obj, emb, n_cls, seed, metric) in dict(trk_a=(8, 9, 32, 2, 1, 'bisoftmax'), trk_b=(10, 14, 64, 3, 2, 'bisoftmax'),
-                                                           trk_c=(6, 7, 16, 1, 3, 'softmax'), trk_d=(6, 7, 16, 2, 4, 'cosine')).items():
+                                                           trk_c=(6, 7, 16, 1, 3, 'softmax'),
+                                                           trk_d=(6, 7, 16, 2, 4, 'cosine')).items() if 'tracker' in which else ():
         trk = Tracker(**dict(CFG, match_metric=metric))
         frames = synth.tracker_sequence(T, n_obj, emb, n_cls, seed)
         out[name + '_case'] = np.array([T, n_obj, emb, n_cls, seed], dtype=np.int64)
@@ -90,7 +136,10 @@ if __name__ == '__main__':
             b, l_, ids = trk.match(bboxes=torch.from_numpy(bb), labels=torch.from_numpy(lab), track_feats=torch.from_numpy(em), frame_id=t)
             out[f'{name}_bboxes{t}'], out[f'{name}_labels{t}'], out[f'{name}_ids{t}'] = b.numpy(), l_.numpy(), ids.numpy()
         print(name, 'ok  tracklets created:', int(trk.num_tracklets), ' last frame ids:', ids.tolist())
-    np.savez_compressed(os.path.join(os.environ.get('VKN_GOLDEN_OUT', os.path.join(ROOT, 'tests', 'golden')), 'qd_tracker.npz'), **out)
+    if 'tracker' in which:
+        np.savez_compressed(os.path.join(GOLDEN_OUT, 'qd_tracker.npz'), **out)
+    if 'embed' not in which:
+        sys.exit(0)
 
     # ---- the embedding head between the update head's tracking kernels and the tracker
     Head = load_reference_embed_head()

@@ -42,7 +42,7 @@ class TrackerOracle:
     def step(self, boxes, labels, embeds, frame_id):
         """boxes [n,5] fp32, labels [n] int64, embeds [n,E] fp32 (torch CPU) -> (boxes [k,5], labels [k], ids [k] int64)."""
         p = self.p
-        order = torch.sort(boxes[:, 4], descending=True)[1]                                   # :139-142
+        order = torch.sort(boxes[:, 4], descending=True, stable=True)[1]                      # :139-142; equal scores: input order (the kernel's rule)
         boxes, labels, embeds = boxes[order], labels[order], embeds[order]
         n = boxes.shape[0]
         ov = iou_matrix(boxes[:, :4], boxes[:, :4])

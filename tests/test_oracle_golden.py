@@ -171,6 +171,37 @@ def test_tracker_oracle_ids_bit_exact_vs_reference():
             assert np.array_equal(l_.numpy(), g[f'{name}_labels{t}']) and np.array_equal(b.numpy(), g[f'{name}_bboxes{t}'])
 
 
+def test_tracker_oracle_bit_exact_vs_reference_on_the_other_axes():
+    """tests/golden/qd_tracker_edges.npz: the reference's own tracker class with with_cats=False, memo_momentum=0.3, three backdrop
+    frames, cosine with frame gaps (four synthetic videos), and on the hand-made threshold videos of tests/tracker_edge_cases.py."""
+    import json
+    import tracker_edge_cases as TC
+    from oracle import synth
+    from oracle.tracker_oracle import TrackerOracle
+    g = dict(np.load(os.path.join(GOLDEN, 'qd_tracker_edges.npz'), allow_pickle=False))
+    assert len(g['video_names']) == 4
+    seen = dict(with_cats=set(), memo_momentum=set(), memo_backdrop_frames=set(), match_metric=set())
+    for name in (str(n) for n in g['video_names']):
+        T, n_obj, emb, n_cls, seed = (int(v) for v in g[name + '_case'])
+        cfg, fids = json.loads(str(g[name + '_cfg'])), g[name + '_frame_ids'].tolist()
+        for k in seen:
+            seen[k].add(cfg[k])
+        trk = TrackerOracle(**cfg)
+        for t, (bb, lab, em, _) in enumerate(synth.tracker_sequence(T, n_obj, emb, n_cls, seed)):
+            b, l_, ids = trk.step(torch.from_numpy(bb), torch.from_numpy(lab), torch.from_numpy(em), fids[t])
+            assert np.array_equal(ids.numpy(), g[f'{name}_ids{t}']), (name, t)
+            assert np.array_equal(l_.numpy(), g[f'{name}_labels{t}']) and np.array_equal(b.numpy(), g[f'{name}_bboxes{t}'])
+    assert seen['with_cats'] == {True, False} and 0.3 in seen['memo_momentum'] and 3 in seen['memo_backdrop_frames']
+    assert seen['match_metric'] == {'bisoftmax', 'softmax', 'cosine'}
+    for name in (str(n) for n in g['case_names']):
+        c = TC.CASES[name]
+        trk = TrackerOracle(**c['cfg'])
+        for t, (fid, bb, lab, em) in enumerate(TC.inputs(c)):
+            b, l_, ids = trk.step(torch.from_numpy(bb), torch.from_numpy(lab), torch.from_numpy(em), fid)
+            assert np.array_equal(ids.numpy(), g[f'case_{name}_ids{t}']), (name, t)
+            assert np.array_equal(l_.numpy(), g[f'case_{name}_labels{t}']) and np.array_equal(b.numpy(), g[f'case_{name}_bboxes{t}'])
+
+
 @pytest.mark.parametrize('name', ['vis_attn_tiny', 'vis_attnpos_tiny', 'vis_attnpos_cfg'])
 def test_query_merge_oracle_matches_reference_golden(name):
     """The clip-level attention query merge (query_merge_method 'attention' / 'attention_pos'): the oracle's restatement on the

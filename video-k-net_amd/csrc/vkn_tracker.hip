@@ -32,6 +32,7 @@ namespace {
 constexpr int TRK_THREADS = 1024;
 constexpr int TRK_MAX_D = 256;      // detections per frame
 constexpr int TRK_MAX_M = 4096;     // memo entries visible to one match (tracklets + backdrops)
+constexpr int TRK_MAX_F = VKN_TRACKER_MAX_BACKDROP_FRAMES;   // backdrop frames: s_bdoff of phase D holds one offset per frame
 
 enum { H_NEXT_ID = 0, H_NTRK = 1, H_NBDF = 2, H_STATUS = 3, H_LAST_NV = 4, H_CALLS = 5, H_WORDS = 16 };
 
@@ -105,7 +106,8 @@ inline int trk_check(const VknTrackerCfg* c) {
     if (c->max_dets <= 0 || c->max_tracklets <= 0 || c->embed_dim <= 0 || c->memo_tracklet_frames < 0 || c->memo_backdrop_frames < 0 ||
         c->match_metric < 0 || c->match_metric > 2)
         return VKN_E_ARG;
-    if (c->max_dets > TRK_MAX_D || trk_mmax(*c) > TRK_MAX_M || c->embed_dim > 1024) return VKN_E_SHAPE;
+    if (c->max_dets > TRK_MAX_D || trk_mmax(*c) > TRK_MAX_M || c->embed_dim > 1024 || c->memo_backdrop_frames > TRK_MAX_F)
+        return VKN_E_SHAPE;
     return VKN_OK;
 }
 
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(TRK_THREADS) void k_qd_match(VknTrackerCfg cfg, cha
     __shared__ float r_max[TRK_MAX_D], r_sum[TRK_MAX_D];
     __shared__ int m_id[TRK_MAX_M], m_label[TRK_MAX_M];
     __shared__ volatile unsigned char m_taken[TRK_MAX_M];
-    __shared__ int s_bdoff[66];
+    __shared__ int s_bdoff[TRK_MAX_F + 1];
     __shared__ int s_nv, s_total, s_any;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;

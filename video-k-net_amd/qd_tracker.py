@@ -31,7 +31,8 @@ def build_tracker(cfg):
 @TRACKERS.register_module()
 class QuasiDenseEmbedTracker:
     """Ctor kwargs of the reference (:11-38) + two capacities of the device memo: `max_dets` detections per frame (<= 256) and
-    `max_tracklets` live tracks (a birth beyond it is dropped and reported through `status`)."""
+    `max_tracklets` live tracks (a birth beyond it is dropped and reported through `status`; the table is tested before the frame's
+    expiry, so a track that expires in the same frame does not make room).  `memo_backdrop_frames` <= 64 on the device."""
 
     def __init__(self, init_score_thr=0.8, obj_score_thr=0.5, match_score_thr=0.5, memo_tracklet_frames=10, memo_backdrop_frames=1,
                  memo_momentum=0.8, nms_conf_thr=0.5, nms_backdrop_iou_thr=0.3, nms_class_iou_thr=0.7, with_cats=True,
@@ -67,7 +68,8 @@ class QuasiDenseEmbedTracker:
         nb, nw = L.vkn_qd_tracker_state_bytes(ctypes.byref(cfg)), L.vkn_qd_tracker_workspace_bytes(ctypes.byref(cfg))
         if nb == 0:
             raise _lib.VknError(-2, 'tracker capacities outside the supported envelope (max_dets <= 256, '
-                                    'max_tracklets + max(memo_backdrop_frames, 1) * max_dets <= 4096, embed_dim <= 1024)')
+                                    'max_tracklets + max(memo_backdrop_frames, 1) * max_dets <= 4096, embed_dim <= 1024, '
+                                    'memo_backdrop_frames <= 64)')
         self._cfg, self._device = cfg, device
         self._state = torch.empty(nb, dtype=torch.uint8, device=device)
         self._ws = torch.empty(nw, dtype=torch.uint8, device=device)
