@@ -299,6 +299,33 @@ def mask_losses(mask_pred, mask_targets, pos_rows, w_mask, w_dice, dice_eps, w_r
     return MaskLossesFn.apply(mask_pred.contiguous(), mask_targets.contiguous(), pos_rows, mask_pred.shape[0], w_mask, w_dice, dice_eps, w_rank)
 
 
+class TrackLossFn(torch.autograd.Function):
+    """(loss_track, loss_track_aux) of the quasi-dense embed head from the embeddings of ALL rows and the assigner's `gt_inds`: one
+    HIP launch sequence forward, one backward (csrc/vkn_trackloss.hip) — no gather, no `nonzero`, no host synchronisation.  The upstream
+    gradients travel as one device [2] tensor; `key_gt`, `ref_gt`, `match`, `match_off` carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, key_embeds, ref_embeds, key_gt, ref_gt, match, match_off, cfg):
+        key_embeds, ref_embeds = key_embeds.contiguous(), ref_embeds.contiguous()
+        losses, _, _, state = ops.track_loss_fwd(cfg, key_embeds, ref_embeds, key_gt, ref_gt, match, match_off)
+        ctx.save_for_backward(key_embeds, ref_embeds, state)
+        ctx.cfg = cfg
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, g_track, g_aux):
+        key_embeds, ref_embeds, state = ctx.saved_tensors
+        gout = torch.stack([g_track.reshape(()), g_aux.reshape(())]).float()
+        d_key, d_ref = ops.track_loss_bwd(ctx.cfg, key_embeds, ref_embeds, state, gout)
+        return d_key, d_ref, None, None, None, None, None
+
+
+def track_loss(key_embeds, ref_embeds, key_gt, ref_gt, match, match_off, cfg):
+    """key_embeds, ref_embeds [B,N,E]; key_gt, ref_gt int64 [B,N]; match int64 [n], match_off int64 [B+1]; cfg `ops.track_loss_cfg`
+    -> (loss_track, loss_track_aux) 0-d tensors (include/vkn_track_train.h)."""
+    return TrackLossFn.apply(key_embeds, ref_embeds, key_gt, ref_gt, match, match_off, cfg)
+
+
 class UpsampleBilinearFn(torch.autograd.Function):
     """`F.interpolate(x, scale_factor=S, mode='bilinear', align_corners=False)` on the HIP kernels, forward and adjoint."""
 

@@ -757,6 +757,73 @@ def track_maps(panoptic_seg, segid, count, ids, n_ids, info, sem_of_label):
     return track_map, semantic_map
 
 
+TRACK_LOSS_MAX_ROWS = _lib.TRACK_LOSS_MAX_ROWS
+
+
+def track_loss_supported(N, E, B=1):
+    """The envelope of `track_loss_fwd` (include/vkn_track_train.h)."""
+    return 1 <= N <= TRACK_LOSS_MAX_ROWS and 4 <= E <= 1024 and E % 4 == 0 and 1 <= B <= 65535
+
+
+def track_loss_cfg(softmax_temp=-1.0, has_aux=True, w_track=1.0, w_aux=1.0, neg_pos_ub=-1, pos_margin=-1.0, neg_margin=-1.0):
+    if int(neg_pos_ub) != neg_pos_ub:
+        raise ValueError(f'neg_pos_ub must be an integer ratio, got {neg_pos_ub}')
+    return _lib.VknTrackLossCfg(float(softmax_temp), int(bool(has_aux)), float(w_track), float(w_aux), int(neg_pos_ub), float(pos_margin),
+                                float(neg_margin))
+
+
+def track_match_offsets(lengths, device):
+    """int64 [B+1] offsets of the concatenated `gt_match_indices` as a device tensor, built from the host-known lengths with fill
+    kernels only (no host-to-device copy: usable under stream capture)."""
+    off = torch.zeros((len(lengths) + 1,), dtype=torch.int64, device=device)
+    for i, n in enumerate(lengths):
+        if n:
+            off[i + 1:] += int(n)
+    return off
+
+
+def track_loss_fwd(cfg, key_embeds, ref_embeds, key_gt, ref_gt, match, match_off, want_kept=False):
+    """The tracking loss of B images in one launch sequence (include/vkn_track_train.h: vkn_track_loss_fwd_f32).  key_embeds, ref_embeds
+    fp32 [B,N,E]; key_gt, ref_gt int64 [B,N] (`gt_inds`: 0 = no ground truth); match int64 [n] / match_off int64 [B+1]: the images'
+    `gt_match_indices` concatenated and their offsets; cfg: `track_loss_cfg(...)`.
+    -> (losses fp32 [2] = (loss_track, loss_track_aux), stats int32 [B,4], aux_kept uint8 [B,N,N] | None, state): `state` is the
+    workspace `track_loss_bwd` reads — a tensor of its own, so that it survives until the backward.  Out-of-range gt / match entries set
+    VKN_STATUS_RANGE in this stream's status word (`workspace_status`)."""
+    ke, re_ = _req(key_embeds, 'key_embeds'), _req(ref_embeds, 'ref_embeds')
+    if ke.dim() != 3 or ke.shape != re_.shape:
+        raise ValueError('key_embeds and ref_embeds must both be [B,N,E]')
+    B, N, E = (int(v) for v in ke.shape)
+    kg, rg = _req_int(key_gt, 'key_gt', torch.int64), _req_int(ref_gt, 'ref_gt', torch.int64)
+    mt, mo = _req_int(match, 'match', torch.int64), _req_int(match_off, 'match_off', torch.int64)
+    if kg.shape != (B, N) or rg.shape != (B, N) or mt.dim() != 1 or mo.shape != (B + 1,):
+        raise ValueError('key_gt / ref_gt must be [B,N], match [n] and match_off [B+1]')
+    dev = ke.device
+    L = _lib.lib()
+    losses = torch.empty((2,), dtype=torch.float32, device=dev)
+    stats = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    kept = torch.empty((B, N, N), dtype=torch.uint8, device=dev) if want_kept else None
+    state = torch.empty((max(L.vkn_track_loss_workspace_bytes(B, N), 256),), dtype=torch.uint8, device=dev)
+    status = _workspace(256, dev)          # the header of this stream's workspace: its first word is the status word
+    with torch.cuda.device(dev):
+        check(L.vkn_track_loss_fwd_f32(ctypes.byref(cfg), _ptr(ke), _ptr(re_), _ptr(kg), _ptr(rg), _ptr(mt), _ptr(mo), int(mt.numel()), B, N, E,
+                                       _ptr(losses), _ptr(stats), _ptr(kept), _ptr(status), _ptr(state), state.numel(), _stream()))
+    return losses, stats, kept, state
+
+
+def track_loss_bwd(cfg, key_embeds, ref_embeds, state, gout):
+    """Gradients of `gout[0] * loss_track + gout[1] * loss_track_aux` w.r.t. the two embedding tensors (vkn_track_loss_bwd_f32).  gout:
+    DEVICE fp32 [2]; state: the forward's.  -> (d_key, d_ref) fp32 [B,N,E], zero on rows without ground truth."""
+    ke, re_, g = _req(key_embeds, 'key_embeds'), _req(ref_embeds, 'ref_embeds'), _req(gout, 'gout')
+    B, N, E = (int(v) for v in ke.shape)
+    if g.numel() != 2:
+        raise ValueError('gout must hold the two upstream gradients')
+    d_key, d_ref = torch.empty_like(ke), torch.empty_like(re_)
+    with torch.cuda.device(ke.device):
+        check(_lib.lib().vkn_track_loss_bwd_f32(ctypes.byref(cfg), _ptr(ke), _ptr(re_), _ptr(g), B, N, E, _ptr(d_key), _ptr(d_ref), _ptr(state),
+                                                state.numel(), _stream()))
+    return d_key, d_ref
+
+
 def panoptic_thing_first(thing_masks, thing_scores, thing_labels, thing_order, stuff_masks, stuff_labels, stuff_order,
                          instance_score_thr, iou_thr, stuff_max_area):
     """Thing-first panoptic merge of ONE image on the device (`merge_stuff_thing`, knet/det/kernel_iter_head.py:385-465).

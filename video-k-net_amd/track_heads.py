@@ -10,7 +10,9 @@ module's parameters, like the [N x C] chain of the update head.  `num_convs > 0`
 provided: every shipped config sets `num_convs=0, roi_feat_size=1` (the "RoI feature" is a kernel).
 
 The training side — `get_track_targets`, `match`, `loss` with `MultiPosCrossEntropyLoss` / `L2Loss`
-(knet/video/qdtrack/losses/{multipos_cross_entropy_loss,l2_loss}.py) — is host-side torch on [K_key x K_ref] matrices.
+(knet/video/qdtrack/losses/{multipos_cross_entropy_loss,l2_loss}.py) — is host-side torch on [K_key x K_ref] matrices; `match_loss`
+/ `match_loss_rows` compute the same losses and their gradients in one forward and one backward launch sequence
+(csrc/vkn_trackloss.hip), without a host synchronisation.
 """
 import numpy as np
 import torch
@@ -219,6 +221,65 @@ class QuasiDenseMaskEmbedHeadGTMask(nn.Module):
         if self.loss_track_aux is not None:
             losses['loss_track_aux'] = loss_track_aux / len(dists)
         return losses
+
+    # ---- the same losses in one forward and one backward launch sequence on the device (csrc/vkn_trackloss.hip)
+    def fused_loss_cfg(self):
+        """The `VknTrackLossCfg` of this head, or None when its losses are not the ones the kernel restates: this package's
+        `MultiPosCrossEntropyLoss(reduction='mean')` and `L2Loss(reduction='mean')` with hard mining or no mining (or no auxiliary
+        loss).  `hard_mining=False` with a positive `neg_pos_ub` draws from NumPy's RNG and stays on the host."""
+        lt, la = self.loss_track, self.loss_track_aux
+        if type(lt) is not MultiPosCrossEntropyLoss or lt.reduction != 'mean':
+            return None
+        ub = -1
+        if la is not None:
+            if type(la) is not L2Loss or la.reduction != 'mean':
+                return None
+            if la.neg_pos_ub > 0:
+                if not la.hard_mining or int(la.neg_pos_ub) != la.neg_pos_ub:
+                    return None
+                ub = int(la.neg_pos_ub)
+        return ops.track_loss_cfg(self.softmax_temp, la is not None, lt.loss_weight, la.loss_weight if la is not None else 0.0, ub,
+                                  la.pos_margin if la is not None else -1.0, la.neg_margin if la is not None else -1.0)
+
+    def match_loss_rows(self, key_embeds, ref_embeds, key_gt_inds, ref_gt_inds, gt_match_indices):
+        """The full-row form: key_embeds, ref_embeds [B,N,E] (this head's outputs for ALL N rows of an image), key_gt_inds, ref_gt_inds
+        int64 [B,N] (the assigner's `gt_inds`: 0 = no ground truth), gt_match_indices: the images' int64 tensors.  -> the dict of `loss`.
+        Every image needs a positive on both sides (the host path asserts there); nothing here reads a value on the host."""
+        from . import autograd
+        cfg = self.fused_loss_cfg()
+        if cfg is None:
+            raise _lib.VknLibraryError('match_loss_rows: this head\'s losses have no fused form (fused_loss_cfg)')
+        B, N, E = key_embeds.shape
+        if not ops.track_loss_supported(N, E, B):
+            raise _lib.VknLibraryError(f'match_loss_rows: [B,N,E] = {(B, N, E)} lies outside vkn_track_loss_fwd_f32')
+        match = torch.cat([m.reshape(-1).to(torch.int64) for m in gt_match_indices])
+        off = ops.track_match_offsets([int(m.numel()) for m in gt_match_indices], key_embeds.device)
+        loss_track, loss_aux = autograd.track_loss(key_embeds, ref_embeds, key_gt_inds, ref_gt_inds, match, off, cfg)
+        losses = dict(loss_track=loss_track)
+        if self.loss_track_aux is not None:
+            losses['loss_track_aux'] = loss_aux
+        return losses
+
+    def match_loss(self, key_embeds, ref_embeds, key_sampling_results, ref_sampling_results, gt_match_indices):
+        """`loss(*match(key_embeds, ref_embeds, ...), *get_track_targets(gt_match_indices, ...))` (:658-716), the same dict.  CUDA fp32
+        embeddings, fusable losses (`fused_loss_cfg`), a positive on both sides of every image and a shape inside the kernel's envelope
+        take the fused path (`match_loss_rows` on the compact rows, zero-padded to the longest image); everything else runs the host
+        methods."""
+        nk = [int(res.pos_assigned_gt_inds.shape[0]) for res in key_sampling_results]
+        nr = [int(res.pos_assigned_gt_inds.shape[0]) for res in ref_sampling_results]
+        N = max(nk + nr + [0])
+        fused = (torch.is_tensor(key_embeds) and key_embeds.is_cuda and ref_embeds.is_cuda and key_embeds.dtype == torch.float32
+                 and ref_embeds.dtype == torch.float32 and key_embeds.dim() == 2 and len(nk) == len(nr) == len(gt_match_indices) > 0
+                 and min(nk + nr) > 0 and ops.track_loss_supported(N, int(key_embeds.shape[1]), len(nk))
+                 and self.fused_loss_cfg() is not None)
+        if not fused:
+            return self.loss(*self.match(key_embeds, ref_embeds, key_sampling_results, ref_sampling_results),
+                             *self.get_track_targets(gt_match_indices, key_sampling_results, ref_sampling_results))
+        ke = torch.stack([F.pad(k, (0, 0, 0, N - k.shape[0])) for k in torch.split(key_embeds, nk)])
+        re_ = torch.stack([F.pad(r, (0, 0, 0, N - r.shape[0])) for r in torch.split(ref_embeds, nr)])
+        kg = torch.stack([F.pad(res.pos_assigned_gt_inds.to(torch.int64) + 1, (0, N - n)) for res, n in zip(key_sampling_results, nk)])
+        rg = torch.stack([F.pad(res.pos_assigned_gt_inds.to(torch.int64) + 1, (0, N - n)) for res, n in zip(ref_sampling_results, nr)])
+        return self.match_loss_rows(ke, re_, kg, rg, gt_match_indices)
 
     random_choice = staticmethod(L2Loss.random_choice)
 
