@@ -12,10 +12,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libvkn.so')
-SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_api.hip')
+SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_api.hip')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn.h')
 TRACK_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_track.h')     # second part of the ABI: the tracking tail
 TRACK_TRAIN_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_track_train.h')     # third part: the tracking loss
+GT_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_gt.h')     # fourth part: the ground truth of a training step
 
 
 class VknLibraryError(RuntimeError):
@@ -104,6 +105,15 @@ TRACK_TRAIN_PROTOS = {k: v for k, v in _protos.items() if k not in PROTOS and k 
 TRACK_TRAIN_SYMBOLS = tuple(TRACK_TRAIN_PROTOS)         # every symbol include/vkn_track_train.h declares
 TRACK_TRAIN_STRUCTS = {k: v for k, v in _structs.items() if k not in STRUCTS}
 CONSTS.update({k: v for k, v in _consts.items() if k not in CONSTS})
+with open(HEADER) as _f, open(TRACK_HEADER) as _g, open(TRACK_TRAIN_HEADER) as _h, open(GT_HEADER) as _i:      # vkn_gt.h: behind the other three
+    _protos, _structs, _consts = read_header(_f.read() + '\n' + _g.read() + '\n' + _h.read() + '\n' + _i.read())
+GT_PROTOS = {k: v for k, v in _protos.items() if k not in PROTOS and k not in TRACK_PROTOS and k not in TRACK_TRAIN_PROTOS}
+GT_SYMBOLS = tuple(GT_PROTOS)               # every symbol include/vkn_gt.h declares
+GT_STRUCTS = {k: v for k, v in _structs.items() if k not in STRUCTS and k not in TRACK_TRAIN_STRUCTS}
+CONSTS.update({k: v for k, v in _consts.items() if k not in CONSTS})
+GT_MAX_IMAGES = CONSTS['VKN_GT_MAX_IMAGES']
+GT_MAX_CLASSES = CONSTS['VKN_GT_MAX_CLASSES']
+GT_MAX_IDS = CONSTS['VKN_GT_MAX_IDS']
 TRACK_LOSS_MAX_ROWS = CONSTS['VKN_TRACK_LOSS_MAX_ROWS']
 TRACK_MAX_K = CONSTS['VKN_TRACK_MAX_K']
 MAX_FCS = CONSTS['VKN_MAX_FCS']
@@ -112,6 +122,7 @@ DW_MAX_ITEMS = CONSTS['VKN_DW_MAX_ITEMS']
 ADAMW_GROUP_ROW = CONSTS['VKN_ADAMW_GROUP_ROW']     # lr, weight_decay, beta1, beta2, eps (fp64)
 MIRRORS = {}                                # struct name -> ctypes.Structure, in the header's order
 TRACK_TRAIN_MIRRORS = {}                    # the structs of include/vkn_track_train.h, kept apart: MIRRORS is what vkn.h declares
+GT_MIRRORS = {}                             # the structs of include/vkn_gt.h, kept apart in the same way
 
 
 def _ctype(base, depth, where, result=False):
@@ -125,6 +136,8 @@ def _ctype(base, depth, where, result=False):
         return ctypes.POINTER(MIRRORS[base])
     if depth == 1 and base in TRACK_TRAIN_MIRRORS:
         return ctypes.POINTER(TRACK_TRAIN_MIRRORS[base])
+    if depth == 1 and base in GT_MIRRORS:
+        return ctypes.POINTER(GT_MIRRORS[base])
     if depth == 0:
         raise VknLibraryError(f'include/vkn.h: {where}: {base!r} by value has no ctypes counterpart here')
     return ctypes.c_void_p
@@ -139,6 +152,11 @@ for _name, _fields in TRACK_TRAIN_STRUCTS.items():
         '__doc__': f'Mirror of include/vkn_track_train.h: {_name}.',
         '_fields_': [(f, _ctype(b, d, _name) * n if n else _ctype(b, d, _name)) for f, b, d, n in _fields]})
 globals().update(TRACK_TRAIN_MIRRORS)       # VknTrackLossCfg
+for _name, _fields in GT_STRUCTS.items():
+    GT_MIRRORS[_name] = type(_name, (ctypes.Structure,), {
+        '__doc__': f'Mirror of include/vkn_gt.h: {_name} (device pointers as integers).',
+        '_fields_': [(f, _ctype(b, d, _name) * n if n else _ctype(b, d, _name)) for f, b, d, n in _fields]})
+globals().update(GT_MIRRORS)                # VknGtImage
 # importable by name: VknDims, VknStageWeights, VknSplitItem, VknDwItem, VknUpdatorNorms, VknUpdatorNormGrads, VknPanopticCfg, VknAssignCfg,
 # VknAssignProblem, VknLsapProblem, VknTailImage, VknTailCfg, VknAdamwItem, VknTrackerCfg
 globals().update(MIRRORS)
@@ -168,7 +186,7 @@ def _hipcc(args, verbose=False, what='hipcc'):
 def _shared_deps(debug):
     """What every object depends on besides csrc/: the public header and, in the debug build, the kernel variants it #includes."""
     exp = os.path.join(os.path.dirname(HERE), 'tools', 'experiments')
-    return [HEADER, TRACK_HEADER, TRACK_TRAIN_HEADER] + ([os.path.join(exp, f) for f in os.listdir(exp)] if debug and os.path.isdir(exp) else [])
+    return [HEADER, TRACK_HEADER, TRACK_TRAIN_HEADER, GT_HEADER] + ([os.path.join(exp, f) for f in os.listdir(exp)] if debug and os.path.isdir(exp) else [])
 
 
 def _stale(path=None):
@@ -245,14 +263,14 @@ def lib():
         raise VknLibraryError(f'{path} is missing — run `python -c "import __graft_entry__ as g; g.build()"` '
                               '(there is deliberately no CPU fallback)')
     L = ctypes.CDLL(path)
-    for name, (result, params) in {**PROTOS, **TRACK_PROTOS, **TRACK_TRAIN_PROTOS}.items():
+    for name, (result, params) in {**PROTOS, **TRACK_PROTOS, **TRACK_TRAIN_PROTOS, **GT_PROTOS}.items():
         fn = getattr(L, name)
         fn.restype = _ctype(*result, name, result=True)
         fn.argtypes = [POINTER_EXCEPTIONS.get((name, p)) or _ctype(base, depth, name) for p, base, depth in params]
     # header vs binary: structs are handed to the kernels verbatim, so a library built from another header means garbage pointers
-    for name, mirror in {**MIRRORS, **TRACK_TRAIN_MIRRORS}.items():
+    for name, mirror in {**MIRRORS, **TRACK_TRAIN_MIRRORS, **GT_MIRRORS}.items():
         probe = 'vkn_sizeof_' + re.sub(r'(?<!^)(?=[A-Z])', '_', name[3:]).lower()
-        if probe not in PROTOS and probe not in TRACK_TRAIN_PROTOS:
+        if probe not in PROTOS and probe not in TRACK_TRAIN_PROTOS and probe not in GT_PROTOS:
             raise VknLibraryError(f'include/vkn.h declares struct {name} without its size probe {probe}()')
         if getattr(L, probe)() != ctypes.sizeof(mirror):
             raise VknLibraryError(f'{path} does not match include/vkn.h: struct {name} is {getattr(L, probe)()} bytes in the library, '

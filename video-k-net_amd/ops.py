@@ -824,6 +824,107 @@ def track_loss_bwd(cfg, key_embeds, ref_embeds, state, gout):
     return d_key, d_ref
 
 
+GT_MAX_IMAGES, GT_MAX_CLASSES, GT_MAX_IDS = _lib.GT_MAX_IMAGES, _lib.GT_MAX_CLASSES, _lib.GT_MAX_IDS
+
+
+def gt_prep_supported(B, Hp, Wp, stride):
+    """The envelope of `gt_classes` / `gt_bank_fill` (include/vkn_gt.h) as far as shapes decide it."""
+    return (1 <= B <= GT_MAX_IMAGES and stride in (1, 2, 4, 8) and Hp >= 1 and Wp >= 1 and Hp % stride == 0 and Wp % stride == 0
+            and Hp * Wp < 2 ** 31 and Hp // stride <= 4 * 65535 and Hp <= 8 * 65535)     # the last two: the grids of the fill / the presence pass
+
+
+def _req_bytes(t, name, dtypes=(torch.uint8,)):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.VknLibraryError(f'{name}: expected a CUDA/HIP tensor — the MI355X path has no CPU fallback')
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8) if t.is_contiguous() else t.contiguous().view(torch.uint8)
+    if t.dtype not in dtypes:
+        raise TypeError(f'{name}: expected one of {dtypes}, got {t.dtype}')
+    return t.contiguous()
+
+
+def gt_classes(sem, valid, label_of_class):
+    """Class presence and stuff labels of B semantic maps (vkn_gt_classes).  sem uint8 / int64 [B,Hp,Wp]; valid: per image
+    (valid_h, valid_w); label_of_class: 256 ints, -1 = skip.  -> (n_sem int32 [B], classes uint8 [B,256], labels int64 [B,256],
+    status int32 [1], raw): the first four are views of / next to `raw`, ONE uint8 buffer that holds status, counts and class lists, so
+    that a caller reads all of them with one copy.  Nothing here synchronises."""
+    sem = _req_bytes(sem, 'sem', (torch.uint8, torch.int64))
+    B, Hp, Wp = (int(v) for v in sem.shape)
+    if len(valid) != B or len(label_of_class) != GT_MAX_CLASSES:
+        raise ValueError('gt_classes: one (valid_h, valid_w) per image and 256 labels')
+    dev = sem.device
+    step = Hp * Wp * sem.element_size()
+    imgs = (_lib.VknGtImage * B)()
+    for b, (vh, vw) in enumerate(valid):
+        imgs[b] = _lib.VknGtImage(None, sem.data_ptr() + b * step, None, 0, 0, 0, int(vh), int(vw), 0, 0, 0)
+    o_n, o_f, o_c = 4, 4 + 4 * B, 4 + 36 * B
+    raw = torch.zeros(o_c + GT_MAX_CLASSES * B, dtype=torch.uint8, device=dev)      # status, n_sem [B], flags [B][8], classes [B][256]
+    labels = torch.empty((B, GT_MAX_CLASSES), dtype=torch.int64, device=dev)
+    table = (ctypes.c_int * GT_MAX_CLASSES)(*[int(v) for v in label_of_class])
+    base = raw.data_ptr()
+    with torch.cuda.device(dev):
+        check(_lib.lib().vkn_gt_classes(imgs, B, Hp, Wp, int(sem.dtype == torch.int64), table, base + o_f, base + o_n, base + o_c,
+                                        _ptr(labels), base, _stream()))
+    return raw[o_n:o_f].view(torch.int32), raw[o_c:].view(B, GT_MAX_CLASSES), labels, raw[:4].view(torch.int32), raw
+
+
+def gt_bank_fill(masks, sem, valid, n_sem, classes, stride, pad_shape, bank=None, device=None):
+    """The fp32 bank [G_total, Hp / stride, Wp / stride] of a step in the training tail's row order (vkn_gt_bank_fill_f32): per image
+    its thing rows, then its stuff rows.  masks: per image uint8 / bool [G_b,Hm_b,Wm_b] or None; sem uint8 / int64 [B,Hp,Wp] or None;
+    valid: per image (valid_h, valid_w); n_sem: per image the HOST count of stuff rows, classes uint8 [B,256] their device class lists
+    (`gt_classes`); pad_shape (Hp, Wp).  -> (bank, thing row0 per image, stuff row0 per image); `bank`: write into this tensor; `device`: where an
+    empty bank lives when there is neither a mask nor a stuff row."""
+    B, (Hp, Wp), s = len(masks), (int(v) for v in pad_shape), int(stride)
+    masks = [None if m is None or m.shape[0] == 0 else _req_bytes(m, 'gt_masks') for m in masks]
+    with_sem = sem is not None and any(n_sem)
+    if with_sem:
+        sem = _req_bytes(sem, 'sem', (torch.uint8, torch.int64))
+        classes = _req_bytes(classes, 'classes')
+        step = Hp * Wp * sem.element_size()
+    dev = next((t.device for t in masks + [sem if with_sem else None, bank] if t is not None), device)
+    imgs = (_lib.VknGtImage * B)()
+    row, row0, sem_row0 = 0, [], []
+    for b, m in enumerate(masks):
+        G, ns = (int(m.shape[0]) if m is not None else 0), (int(n_sem[b]) if with_sem else 0)
+        row0.append(row)
+        sem_row0.append(row + G)
+        imgs[b] = _lib.VknGtImage(m.data_ptr() if G else None, sem.data_ptr() + b * step if ns else None,
+                                  classes.data_ptr() + b * GT_MAX_CLASSES if ns else None, G, int(m.shape[1]) if G else 0,
+                                  int(m.shape[2]) if G else 0, int(valid[b][0]), int(valid[b][1]), ns, row, row + G)
+        row += G + ns
+    if bank is None:
+        bank = torch.empty((row, Hp // s, Wp // s), dtype=torch.float32, device=dev)
+    elif tuple(bank.shape) != (row, Hp // s, Wp // s) or bank.dtype != torch.float32 or not bank.is_contiguous() or not bank.is_cuda:
+        raise ValueError(f'gt_bank_fill: bank must be a contiguous CUDA fp32 [{row}, {Hp // s}, {Wp // s}]')
+    if row:
+        with torch.cuda.device(bank.device):
+            check(_lib.lib().vkn_gt_bank_fill_f32(imgs, B, Hp, Wp, s, int(with_sem and sem.dtype == torch.int64), _ptr(bank), row,
+                                                  _stream()))
+    return bank, row0, sem_row0
+
+
+def gt_match_indices(key_ids, ref_ids):
+    """`gt_match_indices` of B images in one launch (vkn_gt_match_indices): key_ids, ref_ids: per image an int64 tensor of instance
+    ids.  -> (match int64 [sum], match_off int64 [B+1]): per key id the FIRST position among the image's reference ids, else -1 — the
+    pair `track_loss_fwd` takes."""
+    B = len(key_ids)
+    if B != len(ref_ids) or B == 0:
+        raise ValueError('gt_match_indices: one key and one reference id tensor per image')
+    keys = [_req_int(k.reshape(-1), 'key_ids', torch.int64) for k in key_ids]
+    refs = [_req_int(r.reshape(-1), 'ref_ids', torch.int64) for r in ref_ids]
+    dev = keys[0].device
+    kcat = torch.cat(keys) if B > 1 else keys[0]
+    rcat = torch.cat(refs) if B > 1 else refs[0]
+    match = torch.empty_like(kcat)
+    off = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+    klen = (ctypes.c_int * B)(*[int(k.numel()) for k in keys])
+    rlen = (ctypes.c_int * B)(*[int(r.numel()) for r in refs])
+    with torch.cuda.device(dev):
+        check(_lib.lib().vkn_gt_match_indices(_ptr(kcat) if kcat.numel() else None, klen, _ptr(rcat) if rcat.numel() else None, rlen, B,
+                                              _ptr(match) if match.numel() else None, _ptr(off), _stream()))
+    return match, off
+
+
 def panoptic_thing_first(thing_masks, thing_scores, thing_labels, thing_order, stuff_masks, stuff_labels, stuff_order,
                          instance_score_thr, iou_thr, stuff_max_area):
     """Thing-first panoptic merge of ONE image on the device (`merge_stuff_thing`, knet/det/kernel_iter_head.py:385-465).

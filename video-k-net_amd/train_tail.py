@@ -73,6 +73,22 @@ def lowres_ok(shape, stride):
     return stride in (2, 4) and Ns <= 256 and Ns * h * w * 4 < 2 ** 31
 
 
+def _adopt_bank(parts):
+    """The [G_total, H, W] tensor the fp32 `parts` already form — consecutive contiguous views of one storage, in this order — or None.
+    Every part has at least one row (`begin` refuses G_b == 0 and a stuff part is listed only when n_sem > 0): a zero-row view reports a
+    null `data_ptr()` and would end the adoption — such a list gets `torch.cat`, with the same values."""
+    first = parts[0]
+    ptr, storage = first.data_ptr(), first.untyped_storage().data_ptr()
+    for p in parts:
+        if (p.dtype != torch.float32 or not p.is_contiguous() or p.shape[1:] != first.shape[1:] or p.data_ptr() != ptr
+                or p.untyped_storage().data_ptr() != storage or p.requires_grad):
+            return None
+        ptr += p.numel() * 4
+    rows = sum(int(p.shape[0]) for p in parts)
+    H, W = (int(v) for v in first.shape[1:])
+    return first.as_strided((rows, H, W), (H * W, W, 1))
+
+
 class TailStep:
     """The ground truth of one training step, laid out for the fused tail.  `begin` returns None whenever a precondition fails — the
     caller then runs the op-by-op path (same values)."""
@@ -128,7 +144,9 @@ class TailStep:
                 parts.append(gt_sem_seg[b])
                 row += ns
         parts = [p if p.dtype == torch.float32 else p.float() for p in parts]
-        self.bank = torch.cat(parts) if len(parts) > 1 else parts[0].contiguous()           # [G_total, H, W] fp32: ONE copy per step
+        self.bank = _adopt_bank(parts)              # the parts already ARE one bank in this order (`GtPrep`): no copy at all
+        if self.bank is None:
+            self.bank = torch.cat(parts) if len(parts) > 1 else parts[0].contiguous()       # [G_total, H, W] fp32: ONE copy per step
         self.shape = tuple(self.bank.shape[1:])
         # what the assigner reads (cost kernels) — views of the bank: contiguous fp32, no per-stage conversion
         self.gt_views = [self.bank[self.gt_row0[b]:self.gt_row0[b] + self.G[b]] for b in range(self.B)]
