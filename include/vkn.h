@@ -85,8 +85,17 @@ extern "C" {
  * rounding (tests/test_gpu_parity.py::test_persistent_chain_equals_launch_per_gemm_chain), each is deterministic. */
 #define VKN_FLAG_CHAIN_LAUNCHES 256u   /* always one launch per GEMM */
 #define VKN_FLAG_CHAIN_PERSISTENT 512u /* always the persistent kernels (where the shape allows them) */
-#define VKN_FLAG_JOIN_EARLY 32768u     /* vkn_head_forward_*: join the side-stream link BEFORE the x4 upsample instead of behind it (1-3 % slower in back-to-back throughput;
-                                        * the tracking embeddings of a single call are complete as early as its masks) */
+#define VKN_FLAG_JOIN_EARLY 32768u     /* vkn_head_forward_*: join the side-stream link BEFORE the x4 upsample instead of behind it (1.3-2.5 % slower in back-to-back
+                                        * throughput: the upsample then waits for the link's last ~60 us; the tracking embeddings of a single call are complete as
+                                        * early as its masks) */
+/* The tracking link beside the LAST decode.  From 8 frames per call on, where the decode's default grid is exactly one workgroup per CU
+ * (8, 16, 32, 64 ... frames of 128x256; other counts give 198-280 workgroups and are left alone) and x is stored as fp32, when
+ * the link runs on the side stream and is forked right before that decode (the persistent chain), the decode is launched on 192 of the 256 CUs
+ * (vkn_mask_decode_planes_wg_f32's budget) so that the link's LDS-full workgroups find 64 empty CUs at once instead of waiting for the
+ * decode to drain and then running beside — and behind — the x4 upsample.  Same results bit for bit; profiles/link_beside_decode_ab.txt. */
+#define VKN_FLAG_LINK_RESERVE 262144u    /* vkn_head_forward_*: at ANY size at which a side-stream link exists, run the last decode on 3/4 of its default grid
+                                          * (at most 192 workgroups, at least one per frame; where the pixel split cannot shrink, its row split over blockIdx.z goes): tests, A/B */
+#define VKN_FLAG_LINK_NO_RESERVE 524288u /* vkn_head_forward_*: never reserve: the last decode on its default grid (A/B against the earlier behaviour; wins over _RESERVE) */
 #define VKN_FLAG_SCALED_F16 16384u     /* vkn_head_forward_*: `scaled_out` is fp16 [B][N][H*S][W*S] (see vkn_upsample_bilinear_f16out); S in {2, 4} */
 /* The persistent kernels run on the TWO-term fp16 split of both operands (hi + lo, 3 cross products, 4 bytes per weight: vkn_chain_h2.hip;
  * round 5) wherever vkn_prepare_stage_f32 built the fp16 weight images (the C == 256 shapes): 2^-22 per product instead of the 2^-24 of
@@ -216,6 +225,7 @@ int vkn_mask_decode_planes_f32(const float* x, const void* kf_hi, const void* kf
 /*      ... with x stored as x_dtype (VKN_X_F32 / VKN_X_F16 / VKN_X_BF16; see the note at VKN_FLAG_X_F16) */
 int vkn_mask_decode_planes_x(const void* x, int x_dtype, const void* kf_hi, const void* kf_lo, const float* bias, float* out, int B,
                              int N, int C, int P, void* stream);
+/*      ... on a workgroup BUDGET: vkn_mask_decode_planes_wg_f32, include/vkn_decode.h */
 
 /* ---- ops (iii) of stage s and (i) of stage s + 1 as ONE pass over x (k_fused_dg, csrc/vkn_fused.hip): the decode
  *      `F.conv2d(mask_x[i:i+1], mask_feat[i])` knet/det/kernel_update_head.py:247-260, the next stage's binarisation

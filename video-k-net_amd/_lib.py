@@ -17,6 +17,7 @@ HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn.h')
 TRACK_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_track.h')     # second part of the ABI: the tracking tail
 TRACK_TRAIN_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_track_train.h')     # third part: the tracking loss
 GT_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_gt.h')     # fourth part: the ground truth of a training step
+DECODE_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_decode.h')     # fifth part: the decode on a workgroup budget
 
 
 class VknLibraryError(RuntimeError):
@@ -111,6 +112,9 @@ GT_PROTOS = {k: v for k, v in _protos.items() if k not in PROTOS and k not in TR
 GT_SYMBOLS = tuple(GT_PROTOS)               # every symbol include/vkn_gt.h declares
 GT_STRUCTS = {k: v for k, v in _structs.items() if k not in STRUCTS and k not in TRACK_TRAIN_STRUCTS}
 CONSTS.update({k: v for k, v in _consts.items() if k not in CONSTS})
+with open(DECODE_HEADER) as _f:            # vkn_decode.h: prototypes on plain types only, read on its own
+    DECODE_PROTOS, _, _ = read_header(_f.read())
+DECODE_SYMBOLS = tuple(DECODE_PROTOS)       # every symbol include/vkn_decode.h declares
 GT_MAX_IMAGES = CONSTS['VKN_GT_MAX_IMAGES']
 GT_MAX_CLASSES = CONSTS['VKN_GT_MAX_CLASSES']
 GT_MAX_IDS = CONSTS['VKN_GT_MAX_IDS']
@@ -186,7 +190,7 @@ def _hipcc(args, verbose=False, what='hipcc'):
 def _shared_deps(debug):
     """What every object depends on besides csrc/: the public header and, in the debug build, the kernel variants it #includes."""
     exp = os.path.join(os.path.dirname(HERE), 'tools', 'experiments')
-    return [HEADER, TRACK_HEADER, TRACK_TRAIN_HEADER, GT_HEADER] + ([os.path.join(exp, f) for f in os.listdir(exp)] if debug and os.path.isdir(exp) else [])
+    return [HEADER, TRACK_HEADER, TRACK_TRAIN_HEADER, GT_HEADER, DECODE_HEADER] + ([os.path.join(exp, f) for f in os.listdir(exp)] if debug and os.path.isdir(exp) else [])
 
 
 def _stale(path=None):
@@ -263,7 +267,7 @@ def lib():
         raise VknLibraryError(f'{path} is missing — run `python -c "import __graft_entry__ as g; g.build()"` '
                               '(there is deliberately no CPU fallback)')
     L = ctypes.CDLL(path)
-    for name, (result, params) in {**PROTOS, **TRACK_PROTOS, **TRACK_TRAIN_PROTOS, **GT_PROTOS}.items():
+    for name, (result, params) in {**PROTOS, **TRACK_PROTOS, **TRACK_TRAIN_PROTOS, **GT_PROTOS, **DECODE_PROTOS}.items():
         fn = getattr(L, name)
         fn.restype = _ctype(*result, name, result=True)
         fn.argtypes = [POINTER_EXCEPTIONS.get((name, p)) or _ctype(base, depth, name) for p, base, depth in params]

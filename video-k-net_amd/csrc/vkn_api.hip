@@ -1,6 +1,7 @@
 // vkn_api.hip — the C ABI of libvkn.so (include/vkn.h): argument checking, workspace carving and the launch sequence of
 // one stage / of the S-stage loop.  Host code only; every kernel lives in vkn_gather / vkn_update / vkn_decode.
 #include "../../include/vkn.h"
+#include "../../include/vkn_decode.h"
 #include "vkn_common.h"
 #include "vkn_launch.h"
 
@@ -75,6 +76,8 @@ struct StageCall {
     float* up_out = nullptr;
     int up_stride = 0, up_chunk = 0;
     bool* up_done = nullptr;
+    // CUs kept free of the last decode for a side-stream tracking link (link_reserve_wg): 0 never, 1 by policy, 2 always
+    int link_reserve = 0;
     // link options
     const float* prev_obj = nullptr;              // previous-frame kernels of the tracking link; it runs when track_out is given too
     float* track_out = nullptr;
@@ -453,8 +456,10 @@ int run_gather(const VknDims* d, const float* x, const float* masks, const unsig
 // The LAST stage's logits decode from the planes in `s` (+ the caller's xS up-scaled output when up_out is given): in chunks of
 // up_chunk frames, each chunk's upsample right behind its decode, so the upsample reads logits that are still in the memory-side
 // cache.  Odd H*W / VKN_FLAG_REF_KERNELS: the exact-fp32 kernel on s.kern32.
+// max_workgroups: the decode's workgroup budget (0 = its default grid; applies to the one-launch form only).
 int final_decode(const VknDims* d, const float* x, const StageWs& s, const float* kb, float* masks_out, unsigned flags,
-                 hipStream_t st, hipEvent_t prof0, hipEvent_t prof1, float* up_out, int up_stride, int up_chunk, bool* up_done) {
+                 hipStream_t st, hipEvent_t prof0, hipEvent_t prof1, float* up_out, int up_stride, int up_chunk, bool* up_done,
+                 int max_workgroups = 0) {
     const int B = d->B, N = d->N, C = d->C, P = d->H * d->W;
     if ((flags & VKN_FLAG_REF_KERNELS) || (P & 1)) return vkn_launch_decode_ref(x, s.kern32, kb, masks_out, B, N, C, P, st);
     const int ch = (up_out && up_chunk > 0 && up_chunk < B) ? up_chunk : B;
@@ -463,8 +468,8 @@ int final_decode(const VknDims* d, const float* x, const StageWs& s, const float
         const int bn = (B - b0 < ch) ? B - b0 : ch;
         const float* xb = reinterpret_cast<const float*>(reinterpret_cast<const char*>(x) + (size_t)b0 * C * P * (xdt_of(flags) ? 2 : 4));
         if (b0 == 0 && prof0 && hipEventRecord(prof0, st) != hipSuccess) return VKN_E_LAUNCH;  // the (first) decode launch alone
-        VKN_TRY(vkn_launch_decode(xb, s.kfh + b0 * NPTC, s.kfl + b0 * NPTC, kb ? kb + (size_t)b0 * N : nullptr,
-                                  masks_out + (size_t)b0 * N * P, bn, N, C, P, st, xdt_of(flags)));
+        VKN_TRY(vkn_launch_decode_wg(xb, s.kfh + b0 * NPTC, s.kfl + b0 * NPTC, kb ? kb + (size_t)b0 * N : nullptr,
+                                     masks_out + (size_t)b0 * N * P, bn, N, C, P, ch == B ? max_workgroups : 0, st, xdt_of(flags)));
         if (b0 == 0 && prof1 && hipEventRecord(prof1, st) != hipSuccess) return VKN_E_LAUNCH;
         if (ch < B)
             VKN_TRY(vkn_launch_upsample(masks_out + (size_t)b0 * N * P,
@@ -474,6 +479,34 @@ int final_decode(const VknDims* d, const float* x, const StageWs& s, const float
     }
     if (ch < B && up_done) *up_done = true;
     return VKN_OK;
+}
+
+// CUs left to a side-stream tracking link beside the last decode.  That decode holds one LDS-full workgroup on every CU for ~300 us at
+// 32 frames, so the link's own LDS-full workgroups (forked right before it) used to wait for it to drain and then ran beside — and
+// behind — the x4 upsample: 270 us for the link's first GEMM beside the decode, 1.5 ms for the next beside the upsample, FFN + LayerNorm
+// 90-115 us after it, and the next call waited for that tail: ~100 us of every step.  On 192 workgroups the decode is 20-35 us slower
+// (304-310 -> 324-341 us at 32 frames) and the link runs at once on the 64 empty CUs; its last kernels end ~105 us into the upsample,
+// which is no slower for it.  Measured (profiles/link_beside_decode_probe.txt, _ab.txt): whole steps 2.8 / 2.8 / 5.6 % shorter at
+// 32 / 16 / 8 frames per call with 64 CUs reserved; 32 CUs are as good at 32 frames and worse at 16, 96 are worse at 32 and at 8.  The
+// policy covers what was measured: the persistent chain (the fork sits right before the decode), a default decode grid of EXACTLY one
+// workgroup per CU (the 512-px granularity gives 256 workgroups at 8, 16, 32, 64 ... frames of 128x256; at 24 or 28 frames it gives 264
+// and 280, at 9-15 and 17-23 frames 198-253: other regimes, not measured, left alone), 8 frames per call or more, x stored as fp32.
+// With x stored as fp16 the forced reservation was measured AFTER the policy was fixed (+2.1-2.3 % at 8-32 frames, session 3 of the A/B
+// file): a shorter decode window, left disabled in this form.
+// Forced (VKN_FLAG_LINK_RESERVE: tests, A/B) the budget is 3/4 of the default grid, at most 192 and at least one workgroup per frame, so
+// that it changes the launch at small sizes too (where the pixel split cannot shrink, the row split over blockIdx.z goes).
+#define VKN_LINK_RESERVE_CUS 64
+#define VKN_LINK_RESERVE_MIN_FRAMES 8
+inline int link_reserve_wg(const VknDims* d, int mode, bool persistent_chain, unsigned flags) {
+    const VknDecodeSplit dflt = vkn_decode_split(d->B, d->H * d->W, 0);
+    const long long grid = (long long)d->B * dflt.G2;
+    const int full = VKN_DECODE_CUS - VKN_LINK_RESERVE_CUS;
+    if (mode == 2) {
+        const long long q = grid * 3 / 4;
+        return (int)(q > full ? full : (q < d->B ? d->B : q));
+    }
+    if (mode != 1 || !persistent_chain || d->B < VKN_LINK_RESERVE_MIN_FRAMES || xdt_of(flags) != 0) return 0;
+    return grid == VKN_DECODE_CUS ? full : 0;
 }
 
 // The persistent row-owner chain (vkn_chain.hip) covers the shipped shape: C == 256, one cls / mask FC, an FFN whose width is a
@@ -718,7 +751,7 @@ int run_link_ks(const VknDims* d, const VknStageWeights* w, const PrepW& pw, con
 // Emits the stage's masks in the form c.to asks for, from the decode kernels — the f16 planes s.kfh / s.kfl, or fp32 `kern32` where the
 // exact decode runs (ref_decode) — and the folded decode bias `kb` (NULL: none).  `touch` / `touch_bytes`: see StageCall::touch_next.
 int emit_masks(const VknDims* d, const StageCall& c, const StageWs& s, bool ref_decode, const float* kern32, const float* kb,
-               const void* touch, size_t touch_bytes, unsigned flags, hipStream_t st) {
+               const void* touch, size_t touch_bytes, unsigned flags, hipStream_t st, bool persistent_chain = false) {
     const int B = d->B, N = d->N, C = d->C, P = d->H * d->W, xdt = xdt_of(flags);
     if (c.to == TO_KERNELS) {   // the kernels themselves are the output (already in c.kern_out)
         if (c.kb_out && kb && hipMemcpyAsync(c.kb_out, kb, (size_t)B * N * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
@@ -731,7 +764,8 @@ int emit_masks(const VknDims* d, const StageCall& c, const StageWs& s, bool ref_
         return vkn_launch_fused_decode_gather(c.x, s.kfh, s.kfl, kb, d->thr_logit, s.xraw, s.cnt, s.part, s.cntp, B, N, C, P, st, xdt, s.status,
                                               touch, touch_bytes);
     if (c.to == TO_BITS) return vkn_launch_decode_bits(c.x, s.kfh, s.kfl, kb, c.bits_out, d->thr_logit, B, N, C, P, st, xdt);
-    return final_decode(d, c.x, s, kb, c.masks_out, flags, st, c.prof0, c.prof1, c.up_out, c.up_stride, c.up_chunk, c.up_done);
+    return final_decode(d, c.x, s, kb, c.masks_out, flags, st, c.prof0, c.prof1, c.up_out, c.up_stride, c.up_chunk, c.up_done,
+                        link_reserve_wg(d, c.link_reserve, persistent_chain, flags));
 }
 
 int run_stage(const VknDims* d, const StageCall& c, const StageWs& s, unsigned flags, hipStream_t st) {
@@ -802,7 +836,7 @@ int run_stage(const VknDims* d, const StageCall& c, const StageWs& s, unsigned f
                                    chain_h2(pw, flags, have_cls)));
             if (c.obj_ready && hipEventRecord(c.obj_ready, st) != hipSuccess) return VKN_E_LAUNCH;
         }
-        VKN_TRY(emit_masks(d, c, s, ref_decode, s.kern32, kb, touch_nx, touch_nx_bytes, flags, st));
+        VKN_TRY(emit_masks(d, c, s, ref_decode, s.kern32, kb, touch_nx, touch_nx_bytes, flags, st, !fewrow));
         if (link) VKN_TRY(run_track_link(d, s, st, c.obj_out, c.prev_obj, c.track_out, w, c.link_track, c.track_src, xfeat, flags));
         return VKN_OK;
     }
@@ -1048,6 +1082,26 @@ int vkn_mask_decode_planes_x(const void* x, int x_dtype, const void* kf_hi, cons
     if (C % 32 != 0 || C > 256 || N > 256) return VKN_E_SHAPE;
     return vkn_launch_decode(static_cast<const float*>(x), static_cast<const _Float16*>(kf_hi), static_cast<const _Float16*>(kf_lo),
                              bias, out, B, N, C, P, static_cast<hipStream_t>(stream), x_dtype);
+}
+
+int vkn_mask_decode_planes_wg_f32(const float* x, const void* kf_hi, const void* kf_lo, const float* bias, float* out, int B,
+                                  int N, int C, int P, int max_workgroups, void* stream) {
+    return vkn_mask_decode_planes_wg_x(x, VKN_X_F32, kf_hi, kf_lo, bias, out, B, N, C, P, max_workgroups, stream);
+}
+
+int vkn_mask_decode_planes_wg_x(const void* x, int x_dtype, const void* kf_hi, const void* kf_lo, const float* bias, float* out, int B,
+                                int N, int C, int P, int max_workgroups, void* stream) {
+    if (!x || !kf_hi || !kf_lo || !out || B <= 0 || N <= 0 || C <= 0 || P <= 0 || x_dtype < 0 || x_dtype > 2 || max_workgroups < 0)
+        return VKN_E_ARG;
+    if (!aligned16(x) || !aligned16(kf_hi) || !aligned16(kf_lo) || !aligned16(out)) return VKN_E_ALIGN;
+    if (C % 32 != 0 || C > 256 || N > 256) return VKN_E_SHAPE;
+    return vkn_launch_decode_wg(static_cast<const float*>(x), static_cast<const _Float16*>(kf_hi), static_cast<const _Float16*>(kf_lo),
+                                bias, out, B, N, C, P, max_workgroups, static_cast<hipStream_t>(stream), x_dtype);
+}
+
+int vkn_decode_px_per_wg(int B, int P, int max_workgroups) {
+    if (B <= 0 || P <= 0 || max_workgroups < 0) return VKN_E_ARG;
+    return vkn_decode_split(B, P, max_workgroups).px_per_wg;
 }
 
 int vkn_decode_gather_supported(int C, int P) { return vkn_fused_supported(C, P); }
@@ -1620,6 +1674,8 @@ static int head_forward_impl(const VknDims* d, int num_stages, const VknStageWei
     const bool do_a = !ph || (ph & VKN_FLAG_PHASE_A), do_b = !ph || (ph & VKN_FLAG_PHASE_B), do_c = !ph || (ph & VKN_FLAG_PHASE_C);
     if (ph && !(link_pre && (flags & VKN_FLAG_CLIP_LINK) && prev_obj)) return VKN_E_ARG;   // phases exist for the frame-sequential path only
 
+    // CUs for a side-stream tracking link beside the last decode (link_reserve_wg): by policy, forced, or forbidden
+    const int link_reserve = (flags & VKN_FLAG_LINK_NO_RESERVE) ? 0 : ((flags & VKN_FLAG_LINK_RESERVE) ? 2 : 1);
     const float* m_in = mask_preds_in;
     const float* o_in = proposal_feats;
     SideStream* joined = nullptr;
@@ -1683,6 +1739,7 @@ static int head_forward_impl(const VknDims* d, int num_stages, const VknStageWei
             c.prof0 = ev0; c.prof1 = ev1; c.obj_ready = (prev && side) ? side->fork : nullptr;
             c.up_out = up_out; c.up_stride = upsample_stride; c.up_chunk = vkn_dbg_env("VKN_LAST_CHUNK", 0); c.up_done = &up_done;
             c.prev_obj = prev_in_stage; c.track_out = prev_in_stage ? track_out : nullptr;
+            c.link_reserve = (prev && side) ? link_reserve : 0;   // the link is forked onto the side stream before the stage's decode
             VKN_TRY(run_stage(d, c, s, flags, st));
         } else {
             const int N = d->N, C = d->C;
@@ -1703,8 +1760,9 @@ static int head_forward_impl(const VknDims* d, int num_stages, const VknStageWei
             }
             if (!do_c) return VKN_OK;   // phases A / B end here: nothing was forked, nothing to join
             if (prev && side && hipEventRecord(side->fork, st) != hipSuccess) return VKN_E_LAUNCH;
+            // (frame-sequential chains: no measurement of the reservation here, so only the forcing flag applies it)
             VKN_TRY(final_decode(d, x, s, stages[sidx].ft_w ? s.kb : nullptr, m_out, flags, st, ev0, ev1, up_out, upsample_stride,
-                                 vkn_dbg_env("VKN_LAST_CHUNK", 0), &up_done));
+                                 vkn_dbg_env("VKN_LAST_CHUNK", 0), &up_done, link_reserve_wg(d, (prev && side) ? link_reserve : 0, false, flags)));
         }
         m_in = m_out;
         o_in = o_out;
@@ -1739,13 +1797,17 @@ static int head_forward_impl(const VknDims* d, int num_stages, const VknStageWei
             }
         }
     }
-    // Where the side-stream link joins the caller's stream.  Default: BEHIND the upsample — in back-to-back calls the link's tail (its small
-    // launches queue behind the upsample's 100 k workgroups whatever the stream priority: r05 trace, one link GEMM 1.5 ms beside the
-    // upsample, FFN + LayerNorm ~100 us after it) overlaps the next call's first kernels.  VKN_FLAG_JOIN_EARLY joins BEFORE the upsample
-    // (the link then overlaps the cls / mask branches and the decode only, the upsample has the chip to itself): measured 1-3 % SLOWER in
-    // throughput at 1 .. 16 frames per call, equal at 32 (tools/perf_r05.py --what join, docs/LAB_NOTEBOOK.md) — for callers that need the
-    // tracking embeddings of ONE call as early as its masks.  Either way everything the call produced (and every use of the workspace) is
-    // ordered before later work on the caller's stream.
+    // Where the side-stream link joins the caller's stream.  Default: BEHIND the upsample.  Where the last decode left CUs to the link
+    // (link_reserve_wg) the link runs inside the decode's window and its last kernels (k_ffn_fused on 64 CUs, the LayerNorm) end ~105 us
+    // into the upsample, which starts right behind the decode, takes no longer for it and runs alone from there on: nothing trails
+    // it and the next call's first kernel starts when it ends (profiles/link_beside_decode_ab.txt).  Without the reservation the link's
+    // launches queue behind the decode's and then the upsample's workgroups whatever the stream priority — one link GEMM 1.5 ms beside
+    // the upsample, FFN + LayerNorm 90-115 us after it — and that tail DOES delay the next call's first kernel: the join below orders
+    // the caller's stream behind it (traced: the next gather starts 13 us after the link's last kernel, 100-127 us after the upsample).
+    // VKN_FLAG_JOIN_EARLY joins BEFORE the upsample: the upsample then waits for the link's last ~60 us (1.3-2.5 % slower in throughput at
+    // 8 .. 32 frames per call on the built library, profiles/link_beside_decode_ab.txt; 1-1.5 % in the probe) — for callers that need the tracking embeddings of ONE call as
+    // early as its masks.  Either way everything the call produced (and every use of the workspace) is ordered before later work on
+    // the caller's stream.
     const bool join_early = (flags & VKN_FLAG_JOIN_EARLY) != 0;
     if (joined && join_early && hipStreamWaitEvent(st, joined->join, 0) != hipSuccess) return VKN_E_LAUNCH;
     if (scaled_out && upsample_stride > 1 && !up_done)                                    // :122-130

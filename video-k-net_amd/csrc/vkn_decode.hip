@@ -407,7 +407,7 @@ int vkn_launch_decode(const float* x, const _Float16* kfh, const _Float16* kfl, 
 // tensor the N decoded rows are written into (>= N: the caller points `out` at the first of its rows).
 static int decode_launch(const float* x, const _Float16* kfh, const _Float16* kfl, const float* kb, float* out, int B, int N,
                          int C, int P, int shared, int out_rows, unsigned* bits_out, float thr, hipStream_t stream, int xdt,
-                         const float* oscale = nullptr);
+                         const float* oscale = nullptr, int max_workgroups = 0);
 
 // xdt: storage type of x (VKN_X_F32 / VKN_X_F16 / VKN_X_BF16); for the half types `x` points at 2-byte elements
 int vkn_launch_decode_ex(const float* x, const _Float16* kfh, const _Float16* kfl, const float* kb, float* out, int B,
@@ -423,10 +423,33 @@ int vkn_launch_decode_bits(const float* x, const _Float16* kfh, const _Float16* 
     return decode_launch(x, kfh, kfl, kb, nullptr, B, N, C, P, 0, N, bits_out, thr, stream, xdt);
 }
 
+// The split of P over workgroups, see vkn_launch.h.  Default: ceil(B * P / 256) pixels per workgroup in 512-px steps, i.e. 256 workgroups
+// from 256 * 512 pixels on.  Under a budget every frame gets G = max_workgroups / B workgroups (at least one) and each takes
+// ceil(P / G) pixels rounded up to 512: the shares are equal up to the granularity, and rounding UP can only lower the count.
+VknDecodeSplit vkn_decode_split(int B, int P, int max_workgroups) {
+    const long long ppx = ((long long)B * P + VKN_DECODE_CUS - 1) / VKN_DECODE_CUS;
+    int px_per_wg = (int)((ppx + 511) / 512 * 512);  // 8 waves x 64-px tiles
+    if (px_per_wg < 512) px_per_wg = 512;
+    int G2 = (P + px_per_wg - 1) / px_per_wg;
+    if (max_workgroups > 0 && (long long)B * G2 > max_workgroups) {
+        const int G = max_workgroups / B > 0 ? max_workgroups / B : 1;
+        const int share = (P + G - 1) / G;
+        px_per_wg = (share + 511) / 512 * 512;
+        G2 = (P + px_per_wg - 1) / px_per_wg;
+    }
+    return VknDecodeSplit{px_per_wg, G2};
+}
+
+int vkn_launch_decode_wg(const float* x, const _Float16* kfh, const _Float16* kfl, const float* kb, float* out, int B, int N,
+                         int C, int P, int max_workgroups, hipStream_t stream, int xdt) {
+    return decode_launch(x, kfh, kfl, kb, out, B, N, C, P, 0, N, nullptr, 0.f, stream, xdt, nullptr, max_workgroups);
+}
+
 static int decode_launch(const float* x, const _Float16* kfh, const _Float16* kfl, const float* kb, float* out, int B, int N,
                          int C, int P, int shared, int out_rows, unsigned* bits_out, float thr, hipStream_t stream, int xdt,
-                         const float* oscale) {
+                         const float* oscale, int max_workgroups) {
     if (oscale && bits_out) return VKN_E_ARG;
+    if (max_workgroups < 0) return VKN_E_ARG;
     if (B <= 0 || N <= 0 || P <= 0 || out_rows < N) return VKN_E_ARG;
     if (xdt < 0 || xdt > 2) return VKN_E_ARG;
     if (C % 16 != 0 || C > 512 || P < 2 || (P & 1)) return VKN_E_SHAPE;  // odd P: rows not 8-byte aligned (use the ref kernel)
@@ -438,9 +461,9 @@ static int decode_launch(const float* x, const _Float16* kfh, const _Float16* kf
     // boundary costs a store drain + plane staging + first-load latency.  Measured px / workgroup -> us: B = 32: 512 -> 329,
     // 2048 -> 332, 4096 (256 WGs) -> 309; B = 16: 512 -> 161, 2048 (256 WGs) -> 153; B = 8: 512 -> 87, 1024 (256 WGs) -> 88;
     // B <= 4: 512 is best (fewer than 256 WGs either way).  Intermediate sizes (2-4 WGs per CU in sequence) are the slowest.
-    long long ppx = ((long long)B * P + 255) / 256;
-    int px_per_wg = (int)((ppx + 511) / 512 * 512);  // 8 waves x 64-px tiles
-    if (px_per_wg < 512) px_per_wg = 512;
+    // A workgroup budget (max_workgroups > 0, vkn_decode_split) leaves CUs empty on purpose: the head's last decode under a tracking link.
+    const VknDecodeSplit split = vkn_decode_split(B, P, max_workgroups);
+    int px_per_wg = split.px_per_wg;
     const int ppw_dbg = vkn_dbg_env("VKN_DECODE_PXWG", 0);  // debug build only: override pixels per workgroup
     if (ppw_dbg >= 512) px_per_wg = ppw_dbg / 512 * 512;
     const int G2 = (P + px_per_wg - 1) / px_per_wg;
@@ -458,6 +481,8 @@ static int decode_launch(const float* x, const _Float16* kfh, const _Float16* kf
     if (!bits_out && NPT <= 128 && (long long)B * G2 <= 128) {
         znb = ((long long)B * G2 <= 64) ? 1 : 2;
         if (NPT % (znb * 32) != 0 || NPT / (znb * 32) < 2) znb = 0;
+        // a budget is a budget on the WHOLE grid: the row split multiplies it by NPT / (znb * 32), so it goes where that does not fit
+        if (znb && max_workgroups > 0 && (long long)B * G2 * (NPT / (znb * 32)) > max_workgroups) znb = 0;
     }
     for (int n0 = 0; n0 < NPT; n0 += 128) {
         const int nb = znb ? znb : ((NPT - n0 >= 128) ? 4 : (NPT - n0) / 32);

@@ -78,6 +78,20 @@ struct VknDecodeStrides {
 // half types `x` points at 2-byte elements
 int vkn_launch_decode_ex(const float* x, const _Float16* kfh, const _Float16* kfl, const float* kb, float* out, int B, int N,
                          int C, int P, int shared, int out_rows, hipStream_t stream, int xdt = 0, const float* oscale = nullptr);
+// CUs the persistent grids are sized for (one LDS-full workgroup each)
+#define VKN_DECODE_CUS 256
+// How a decode launch splits a frame's P pixels over workgroups: G2 workgroups per frame (the same for every frame) of px_per_wg
+// pixels each, px_per_wg a multiple of the kernel's 512-px granularity (8 waves x 64-px tiles), G2 * px_per_wg >= P.
+// max_workgroups == 0: the default (one workgroup per CU over the whole batch once it is large enough); > 0: B * G2 <= max_workgroups
+// wherever max_workgroups >= B, by an even split of P.  Pure host arithmetic.  (The launcher also drops the few-frame row split over
+// blockIdx.z where the whole grid would not fit the budget with it.)
+struct VknDecodeSplit {
+    int px_per_wg, G2;
+};
+VknDecodeSplit vkn_decode_split(int B, int P, int max_workgroups);
+// vkn_launch_decode under a workgroup budget (0 = vkn_launch_decode); bit-identical output whatever the split
+int vkn_launch_decode_wg(const float* x, const _Float16* kfh, const _Float16* kfl, const float* kb, float* out, int B, int N,
+                         int C, int P, int max_workgroups, hipStream_t stream, int xdt = 0);
 int vkn_launch_decode_ref_ex(const float* x, const float* kern, const float* kb, float* out, int B, int N, int C, int P,
                              int shared, int out_rows, hipStream_t stream);
 int vkn_launch_decode_bits(const float* x, const _Float16* kfh, const _Float16* kfl, const float* kb, unsigned* bits_out,

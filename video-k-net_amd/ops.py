@@ -20,7 +20,9 @@ FLAG_LOGITS_HANDOFF = _H['VKN_FLAG_LOGITS_HANDOFF']
 FLAG_BITS_HANDOFF = _H['VKN_FLAG_BITS_HANDOFF']
 FLAG_CHAIN_LAUNCHES = _H['VKN_FLAG_CHAIN_LAUNCHES']      # the [N x C] chain always as one launch per GEMM (default: by row count, include/vkn.h)
 FLAG_CHAIN_PERSISTENT = _H['VKN_FLAG_CHAIN_PERSISTENT']  # ... always as the two persistent row-owner kernels (vkn_chain.hip)
-FLAG_JOIN_EARLY = _H['VKN_FLAG_JOIN_EARLY']              # head_forward: the side-stream link joins BEFORE the upsample (single-call latency; 1-3 % slower in throughput)
+FLAG_JOIN_EARLY = _H['VKN_FLAG_JOIN_EARLY']              # head_forward: the side-stream link joins BEFORE the upsample (single-call latency; 1.3-2.5 % slower in throughput)
+FLAG_LINK_RESERVE = _H['VKN_FLAG_LINK_RESERVE']          # head_forward: the last decode on 3/4 of its default grid (at most 192 workgroups) at ANY size with a side-stream link (default: 192 of 256 from 8 frames on; tests, A/B)
+FLAG_LINK_NO_RESERVE = _H['VKN_FLAG_LINK_NO_RESERVE']    # head_forward: ... never (A/B against the default grid of the last decode)
 FLAG_SCALED_F16 = _H['VKN_FLAG_SCALED_F16']              # head_forward: the up-scaled logits as fp16 (vkn_upsample_bilinear_f16out)
 FLAG_CHAIN_BF16X3 = _H['VKN_FLAG_CHAIN_BF16X3']          # ... the persistent kernels on the three-term bf16 split of rounds 2-4 (default since round 5: the two-term fp16 split, vkn_chain_h2.hip)
 FLAG_INIT_SEPARATE = _H['VKN_FLAG_INIT_SEPARATE']        # vkn_kernel_init_f32: the round-5 form of pass 0 (separate decodes + add + logits gather) instead of the one-pass kernel (A/B)
@@ -559,6 +561,26 @@ def mask_decode_planes(x, hi, lo, N, bias=None, out=None):
         check(_lib.lib().vkn_mask_decode_planes_x(_ptr(x), xdt, _ptr(hi), _ptr(lo), _ptr(bias), _ptr(out), B, N, C, H * W,
                                                   _stream()))
     return out
+
+
+def mask_decode_planes_wg(x, hi, lo, N, max_workgroups, bias=None, out=None):
+    """mask_decode_planes on at most `max_workgroups` workgroups (0: the default split): bit-identical output whatever the split."""
+    x, xdt = _req_x(x)
+    B, C, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, N, H, W), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        check(_lib.lib().vkn_mask_decode_planes_wg_x(_ptr(x), xdt, _ptr(hi), _ptr(lo), _ptr(bias), _ptr(out), B, N, C, H * W,
+                                                     int(max_workgroups), _stream()))
+    return out
+
+
+def decode_px_per_wg(B, P, max_workgroups=0):
+    """Pixels per workgroup of a decode launch over B frames of P pixels under a workgroup budget (host arithmetic only)."""
+    r = _lib.lib().vkn_decode_px_per_wg(int(B), int(P), int(max_workgroups))
+    if r < 0:
+        check(r)
+    return r
 
 
 def decode_gather(x, hi, lo, N, bias=None, hard_mask_thr=0.5):
