@@ -57,20 +57,3 @@ def test_split_rejects_bad_arguments(vkn):
     for args in ((0, 512, 0), (1, 0, 0), (1, 512, -1)):
         with pytest.raises(vkn._lib.VknError):
             vkn.ops.decode_px_per_wg(*args)
-
-
-def test_decode_header_is_exported(vkn):
-    """include/vkn_decode.h declares exactly the decode-on-a-budget symbols, the library exports them with the header's argument lists, and
-    the first part of the ABI comes out unchanged"""
-    import ctypes
-    lib = vkn._lib
-    new = {'vkn_mask_decode_planes_wg_f32', 'vkn_mask_decode_planes_wg_x', 'vkn_decode_px_per_wg'}
-    assert set(lib.DECODE_SYMBOLS) == new and set(lib.DECODE_PROTOS) == new
-    assert len(lib.SYMBOLS) == 111 and not new & (set(lib.SYMBOLS) | set(lib.TRACK_SYMBOLS) | set(lib.TRACK_TRAIN_SYMBOLS) | set(lib.GT_SYMBOLS))
-    raw = ctypes.CDLL(lib.LIBPATH)
-    for sym in new:
-        assert getattr(raw, sym) is not None
-    L = lib.lib()
-    assert len(L.vkn_mask_decode_planes_wg_f32.argtypes) == 11 and len(L.vkn_mask_decode_planes_wg_x.argtypes) == 12
-    assert len(L.vkn_decode_px_per_wg.argtypes) == 3
-    assert (lib.CONSTS['VKN_FLAG_LINK_RESERVE'], lib.CONSTS['VKN_FLAG_LINK_NO_RESERVE']) == (262144, 524288)

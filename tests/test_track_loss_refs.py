@@ -2,8 +2,6 @@
 against the reference's goldens and against the package's host path, the premises the GPU tests build on (mining active, an
 unambiguous cut), and what the third part of the C ABI (include/vkn_track_train.h) promises before any launch."""
 import ctypes
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,7 +9,6 @@ import torch
 
 import track_loss_ref as R
 
-ROOT = R.ROOT
 E_ARG, E_SHAPE, E_WS, E_ALIGN = -1, -2, -3, -5
 
 
@@ -113,42 +110,6 @@ def test_match_loss_without_a_device_is_the_host_path(vkn):
 
 
 # ---------------------------------------------------------------------------------------------------- the ABI, before any launch
-def test_track_train_header_is_exported(vkn):
-    """The library exports every function include/vkn_track_train.h declares, the binding reads them from the header, and the other
-    two parts of the ABI come out unchanged."""
-    lib = vkn._lib
-    assert set(lib.TRACK_TRAIN_SYMBOLS) == {'vkn_sizeof_track_loss_cfg', 'vkn_track_loss_workspace_bytes', 'vkn_track_loss_fwd_f32',
-                                            'vkn_track_loss_bwd_f32'}
-    assert len(lib.SYMBOLS) == 111 and len(lib.TRACK_SYMBOLS) == 5
-    assert not set(lib.TRACK_TRAIN_SYMBOLS) & (set(lib.SYMBOLS) | set(lib.TRACK_SYMBOLS))
-    assert 'VknTrackLossCfg' not in lib.MIRRORS and lib.TRACK_LOSS_MAX_ROWS == 128
-    raw = ctypes.CDLL(lib.LIBPATH)
-    for sym in lib.TRACK_TRAIN_SYMBOLS:
-        assert getattr(raw, sym) is not None
-    L = lib.lib()
-    with open(lib.TRACK_TRAIN_HEADER) as f:
-        protos, structs, _ = lib.read_header(open(lib.HEADER).read() + open(lib.TRACK_HEADER).read() + f.read())
-    for sym in lib.TRACK_TRAIN_SYMBOLS:
-        assert len(getattr(L, sym).argtypes) == len(protos[sym][1]), sym
-    assert len(L.vkn_track_loss_fwd_f32.argtypes) == 18 and len(L.vkn_track_loss_bwd_f32.argtypes) == 12
-    assert L.vkn_track_loss_fwd_f32.argtypes[0]._type_ is lib.VknTrackLossCfg
-    assert [f for f, *_ in structs['VknTrackLossCfg']] == ['softmax_temp', 'has_aux', 'w_track', 'w_aux', 'neg_pos_ub', 'pos_margin', 'neg_margin']
-    assert L.vkn_sizeof_track_loss_cfg() == ctypes.sizeof(lib.VknTrackLossCfg) == 28
-    assert L.vkn_track_loss_workspace_bytes.restype is ctypes.c_size_t
-
-
-def test_track_train_header_is_c99(tmp_path):
-    """include/vkn_track_train.h is plain C on top of the other two."""
-    gcc = shutil.which('gcc')
-    if gcc is None:
-        pytest.skip('no gcc in this environment')
-    src = tmp_path / 'use_track_train.c'
-    src.write_text('#include "include/vkn_track_train.h"\nint main(void) { VknTrackLossCfg c; c.has_aux = VKN_TRACK_LOSS_MAX_ROWS; '
-                   'return c.has_aux > VKN_TRACK_MAX_K ? 1 : 0; }\n')
-    r = subprocess.run([gcc, '-std=c99', '-Wall', '-Wextra', '-Werror', '-fsyntax-only', '-I', ROOT, str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
 def test_track_loss_entries_refuse_before_any_launch(vkn):
     """NULL pointers, shapes outside the envelope, misaligned pointers and a short workspace are refused by the host-side checks, in this
     order, before a pointer is looked at (the fake pointers below are never dereferenced)."""

@@ -3,9 +3,6 @@
 tests build on (exactness of the dyadic inputs, near-tie share of the non-dyadic ones).  Plus what the new part of the C ABI
 promises before any launch."""
 import ctypes
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,7 +10,6 @@ import torch
 
 import track_tail_refs as R
 
-ROOT = R.ROOT
 T, S = 2, 3       # thing / stuff classes of the hand-made frames
 
 
@@ -157,35 +153,6 @@ def test_nondyadic_inputs_keep_the_near_tie_cap(case):
 
 
 # ---------------------------------------------------------------------------------------------------- the ABI, before any launch
-def test_track_header_is_exported(vkn):
-    """The library exports every function include/vkn_track.h declares, and the binding reads them from the header (no hand-written
-    prototype)."""
-    lib = vkn._lib
-    assert set(lib.TRACK_SYMBOLS) == {'vkn_track_boxes_workspace_bytes', 'vkn_track_boxes_f32', 'vkn_track_maps_workspace_bytes',
-                                      'vkn_track_maps_i32', 'vkn_qd_tracker_match_dev_f32'}
-    assert not set(lib.TRACK_SYMBOLS) & set(lib.SYMBOLS)
-    raw = ctypes.CDLL(lib.LIBPATH)
-    for sym in lib.TRACK_SYMBOLS:
-        assert getattr(raw, sym) is not None
-    L = lib.lib()
-    assert len(L.vkn_track_boxes_f32.argtypes) == 21 and len(L.vkn_track_maps_i32.argtypes) == 18
-    assert len(L.vkn_qd_tracker_match_dev_f32.argtypes) == 16
-    assert L.vkn_qd_tracker_match_dev_f32.argtypes[0] is ctypes.POINTER(lib.VknTrackerCfg) or \
-        L.vkn_qd_tracker_match_dev_f32.argtypes[0]._type_ is lib.VknTrackerCfg
-    assert L.vkn_track_boxes_workspace_bytes.restype is ctypes.c_size_t
-
-
-def test_track_header_is_c99(tmp_path):
-    """include/vkn_track.h is plain C on top of vkn.h."""
-    gcc = shutil.which('gcc')
-    if gcc is None:
-        pytest.skip('no gcc in this environment')
-    src = tmp_path / 'use_track.c'
-    src.write_text('#include "include/vkn_track.h"\nint main(void) { return VKN_TRACK_MAX_K > 0 ? 0 : 1; }\n')
-    r = subprocess.run([gcc, '-std=c99', '-Wall', '-Wextra', '-Werror', '-fsyntax-only', '-I', ROOT, str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-
-
 def test_tracker_device_count_entry_refuses_before_any_launch(vkn):
     """vkn_qd_tracker_match_dev_f32: every pointer is required, n_max lies in [1, max_dets]; checked on the host (fake pointers)."""
     L = vkn._lib.lib()

@@ -1,8 +1,11 @@
-"""ctypes binding of libvkn.so, computed from its C ABI in include/vkn.h, + the hipcc build recipe.
+"""ctypes binding of libvkn.so, computed from its C ABI in the headers `ABI_HEADERS` under include/, + the hipcc build recipe.
+`ABI` maps each header to what its own text declares (prototypes, structs, constants, ctypes mirrors); a header is read once, knowing
+the headers it #includes, and no name may be declared twice.  `PROTOS`, `SYMBOLS`, `STRUCTS`, `MIRRORS` are include/vkn.h's part.
 
 The library is built IN-TREE (`video-k-net_amd/lib/libvkn.so`) so that it travels with the repo snapshot to the GPU
 box; there is no CPU fallback: if the library is missing every op raises `VknLibraryError`.
 """
+import collections
 import ctypes
 import os
 import re
@@ -13,11 +16,9 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libvkn.so')
 SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_api.hip')
-HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn.h')
-TRACK_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_track.h')     # second part of the ABI: the tracking tail
-TRACK_TRAIN_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_track_train.h')     # third part: the tracking loss
-GT_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_gt.h')     # fourth part: the ground truth of a training step
-DECODE_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'vkn_decode.h')     # fifth part: the decode on a workgroup budget
+INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
+# The C ABI, one header per part, each behind the headers it #includes.  A new part is one more name here.
+ABI_HEADERS = ('vkn.h', 'vkn_track.h', 'vkn_track_train.h', 'vkn_gt.h', 'vkn_decode.h')
 
 
 class VknLibraryError(RuntimeError):
@@ -30,12 +31,13 @@ class VknError(RuntimeError):
         self.code = code
 
 
-# ---- the reader of include/vkn.h.  Everything here that restates the C ABI (prototypes, struct mirrors, constants) is computed from
-#      the header by it, once per process.  It knows exactly the C subset the header is written in and refuses the rest.
+# ---- the reader of include/*.h.  Everything here that restates the C ABI (prototypes, struct mirrors, constants) is computed from
+#      the headers by it, once per process.  It knows exactly the C subset they are written in and refuses the rest.
 _SCALARS = {'int': ctypes.c_int, 'unsigned': ctypes.c_uint, 'unsigned int': ctypes.c_uint, 'size_t': ctypes.c_size_t,
             'float': ctypes.c_float, 'double': ctypes.c_double, 'long long': ctypes.c_longlong}
-_POINTEES = {'void', 'char', 'unsigned char', 'int64_t'}     # types the header only ever points at
+_POINTEES = {'void', 'char', 'unsigned char', 'int64_t'}     # types the headers only ever point at
 _DECLARATOR = re.compile(r'([\w\s]*?)\s*((?:\*\s*(?:const\b\s*)?)*)(\w+)\s*(?:\[(\w+)\])?')
+_COMMENT = re.compile(r'/\*.*?\*/|//[^\n]*', flags=re.S)
 
 
 def _int(text, consts, where):
@@ -44,7 +46,7 @@ def _int(text, consts, where):
     for term in text.strip('() \t').split('|'):
         term = term.strip()
         if not (term in consts or re.fullmatch(r'-?\d+|\d+u|0x[0-9a-fA-F]+', term)):
-            raise VknLibraryError(f'include/vkn.h: {where}: {text.strip()!r} is not an integer this binding can read')
+            raise VknLibraryError(f'{where}: {text.strip()!r} is not an integer this binding can read')
         total |= consts[term] if term in consts else int(term.rstrip('u'), 0)
     return total
 
@@ -57,64 +59,77 @@ def _declaration(decl, known, consts, where):
         words = [w for w in m.group(1).split() if w != 'const'] if m else []
         base = ' '.join(words) or base
         if not m or bool(words) == bool(out) or base not in known:      # the type comes first, and only first
-            raise VknLibraryError(f'include/vkn.h: {where}: cannot read the declaration {" ".join(decl.split())!r}')
+            raise VknLibraryError(f'{where}: cannot read the declaration {" ".join(decl.split())!r}')
         out.append((m.group(3), base, m.group(2).count('*'), m.group(4) and _int(m.group(4), consts, where)))
     return out
 
 
-def read_header(text):
-    """(prototypes, structs, constants) of a header written in vkn.h's C subset:
+def read_header(text, known_structs=(), known_consts=(), where='include/vkn.h'):
+    """(prototypes, structs, constants) that a header written in vkn.h's C subset declares itself:
     prototypes {function: ((base type, pointer depth) of the result, [(parameter, base type, pointer depth)])},
     structs {name: [(field, base type, pointer depth, array length or None)]}, constants {VKN_*: int}; all in the header's order.
+    `known_structs` (names) and `known_consts` ({VKN_*: int}) are what the headers it #includes declare; `where` names it in errors.
     Raises VknLibraryError naming the declaration it cannot read."""
-    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
-    consts, structs, protos, known = {}, {}, {}, set(_SCALARS) | _POINTEES
+    text = _COMMENT.sub(' ', text)
+    consts, structs, protos, known, values = {}, {}, {}, set(_SCALARS) | _POINTEES | set(known_structs), dict(known_consts)
     for name, value in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(VKN_\w+)(.*)$', text, flags=re.M):
         if value.strip():                                               # (the include guard has no value)
-            consts[name] = _int(value, consts, name)
+            consts[name] = values[name] = _int(value, values, f'{where}: {name}')
     text = re.sub(r'#ifdef __cplusplus.*?#endif', '', text, flags=re.S)
     text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
 
     def struct(m):
-        structs[m.group(2)] = [f for d in m.group(1).split(';') if d.strip() for f in _declaration(d, known, consts, m.group(2))]
+        structs[m.group(2)] = [f for d in m.group(1).split(';') if d.strip() for f in _declaration(d, known, values, f'{where}: {m.group(2)}')]
         known.add(m.group(2))
         return ''
     text = re.sub(r'typedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;', struct, text)
     for decl in filter(None, (' '.join(d.split()) for d in text.split(';'))):
         m = re.fullmatch(r'([\w\s\*]+?)\b(vkn_\w+)\s*\(([^()]*)\)', decl)
         if not m:
-            raise VknLibraryError(f'include/vkn.h: cannot read the declaration {decl[:120]!r}')
-        (_, rbase, rdepth, _), = _declaration(m.group(1) + ' result', known, consts, m.group(2))
-        params = [] if m.group(3).strip() == 'void' else [q for p in m.group(3).split(',') for q in _declaration(p, known, consts, m.group(2))]
+            raise VknLibraryError(f'{where}: cannot read the declaration {decl[:120]!r}')
+        at = f'{where}: {m.group(2)}'
+        (_, rbase, rdepth, _), = _declaration(m.group(1) + ' result', known, values, at)
+        params = [] if m.group(3).strip() == 'void' else [q for p in m.group(3).split(',') for q in _declaration(p, known, values, at)]
         if any(length is not None for *_, length in params):
-            raise VknLibraryError(f'include/vkn.h: {m.group(2)}: array parameters are not supported')
+            raise VknLibraryError(f'{at}: array parameters are not supported')
         protos[m.group(2)] = ((rbase, rdepth), [q[:3] for q in params])
     return protos, structs, consts
 
 
-with open(HEADER) as _f:
-    PROTOS, STRUCTS, CONSTS = read_header(_f.read())
-SYMBOLS = tuple(PROTOS)                     # every symbol include/vkn.h declares
-with open(HEADER) as _f, open(TRACK_HEADER) as _g:          # vkn_track.h builds on vkn.h's structs: read behind it, keep what it adds
-    _protos, _, _consts = read_header(_f.read() + '\n' + _g.read())
-TRACK_PROTOS = {k: v for k, v in _protos.items() if k not in PROTOS}
-TRACK_SYMBOLS = tuple(TRACK_PROTOS)         # every symbol include/vkn_track.h declares
-CONSTS.update({k: v for k, v in _consts.items() if k not in CONSTS})
-with open(HEADER) as _f, open(TRACK_HEADER) as _g, open(TRACK_TRAIN_HEADER) as _h:      # vkn_track_train.h: read behind the other two
-    _protos, _structs, _consts = read_header(_f.read() + '\n' + _g.read() + '\n' + _h.read())
-TRACK_TRAIN_PROTOS = {k: v for k, v in _protos.items() if k not in PROTOS and k not in TRACK_PROTOS}
-TRACK_TRAIN_SYMBOLS = tuple(TRACK_TRAIN_PROTOS)         # every symbol include/vkn_track_train.h declares
-TRACK_TRAIN_STRUCTS = {k: v for k, v in _structs.items() if k not in STRUCTS}
-CONSTS.update({k: v for k, v in _consts.items() if k not in CONSTS})
-with open(HEADER) as _f, open(TRACK_HEADER) as _g, open(TRACK_TRAIN_HEADER) as _h, open(GT_HEADER) as _i:      # vkn_gt.h: behind the other three
-    _protos, _structs, _consts = read_header(_f.read() + '\n' + _g.read() + '\n' + _h.read() + '\n' + _i.read())
-GT_PROTOS = {k: v for k, v in _protos.items() if k not in PROTOS and k not in TRACK_PROTOS and k not in TRACK_TRAIN_PROTOS}
-GT_SYMBOLS = tuple(GT_PROTOS)               # every symbol include/vkn_gt.h declares
-GT_STRUCTS = {k: v for k, v in _structs.items() if k not in STRUCTS and k not in TRACK_TRAIN_STRUCTS}
-CONSTS.update({k: v for k, v in _consts.items() if k not in CONSTS})
-with open(DECODE_HEADER) as _f:            # vkn_decode.h: prototypes on plain types only, read on its own
-    DECODE_PROTOS, _, _ = read_header(_f.read())
-DECODE_SYMBOLS = tuple(DECODE_PROTOS)       # every symbol include/vkn_decode.h declares
+AbiHeader = collections.namedtuple('AbiHeader', 'path protos symbols structs consts mirrors')      # what ONE header's own text declares
+
+
+def read_abi(include_dir, names):
+    """{header name: AbiHeader} of the headers `names` under `include_dir`, each read once, in order.  A header is read knowing the
+    structs and constants of the headers its own `#include "..."` lines name, transitively (`<...>` includes are the C library's and
+    are ignored).  Raises VknLibraryError when a header includes a file that is not earlier in `names`, and when two headers declare
+    the same function, struct or constant.  `mirrors` is left empty: building the ctypes classes is the caller's step."""
+    abi, deps, owner = {}, {}, {}
+    for name in names:
+        with open(os.path.join(include_dir, name)) as f:
+            text = f.read()
+        deps[name] = []
+        for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', _COMMENT.sub(' ', text), flags=re.M):
+            if inc not in abi:
+                raise VknLibraryError(f'include/{name} includes "{inc}", which is not among the headers listed before it: {tuple(abi)}')
+            deps[name] += [d for d in deps[inc] + [inc] if d not in deps[name]]
+        protos, structs, consts = read_header(text, [s for d in deps[name] for s in abi[d].structs],
+                                              {k: v for d in deps[name] for k, v in abi[d].consts.items()}, f'include/{name}')
+        for declared in (*protos, *structs, *consts):
+            if owner.setdefault(declared, name) != name:
+                raise VknLibraryError(f'{declared} is declared twice: by include/{owner[declared]} and by include/{name}')
+        abi[name] = AbiHeader(f.name, protos, tuple(protos), structs, consts, {})
+    return abi
+
+
+def _each(field):
+    """[(header, name, value)] of one field of every header's record, in the headers' order"""
+    return [(h, k, v) for h, hdr in ABI.items() for k, v in getattr(hdr, field).items()]
+
+
+ABI = read_abi(INCLUDE, ABI_HEADERS)
+HEADER, PROTOS, SYMBOLS, STRUCTS, MIRRORS = (getattr(ABI['vkn.h'], k) for k in ('path', 'protos', 'symbols', 'structs', 'mirrors'))
+CONSTS = {k: v for _, k, v in _each('consts')}      # every header's constants: no name is declared twice
 GT_MAX_IMAGES = CONSTS['VKN_GT_MAX_IMAGES']
 GT_MAX_CLASSES = CONSTS['VKN_GT_MAX_CLASSES']
 GT_MAX_IDS = CONSTS['VKN_GT_MAX_IDS']
@@ -124,9 +139,7 @@ MAX_FCS = CONSTS['VKN_MAX_FCS']
 SPLIT_MAX_ITEMS = CONSTS['VKN_SPLIT_MAX_ITEMS']
 DW_MAX_ITEMS = CONSTS['VKN_DW_MAX_ITEMS']
 ADAMW_GROUP_ROW = CONSTS['VKN_ADAMW_GROUP_ROW']     # lr, weight_decay, beta1, beta2, eps (fp64)
-MIRRORS = {}                                # struct name -> ctypes.Structure, in the header's order
-TRACK_TRAIN_MIRRORS = {}                    # the structs of include/vkn_track_train.h, kept apart: MIRRORS is what vkn.h declares
-GT_MIRRORS = {}                             # the structs of include/vkn_gt.h, kept apart in the same way
+_MIRROR = {}                                # struct name -> ctypes.Structure, of every header: where _ctype looks a struct up
 
 
 def _ctype(base, depth, where, result=False):
@@ -136,34 +149,21 @@ def _ctype(base, depth, where, result=False):
         return _SCALARS[base]
     if depth == 1 and base == 'char' and result:
         return ctypes.c_char_p
-    if depth == 1 and base in MIRRORS:
-        return ctypes.POINTER(MIRRORS[base])
-    if depth == 1 and base in TRACK_TRAIN_MIRRORS:
-        return ctypes.POINTER(TRACK_TRAIN_MIRRORS[base])
-    if depth == 1 and base in GT_MIRRORS:
-        return ctypes.POINTER(GT_MIRRORS[base])
+    if depth == 1 and base in _MIRROR:
+        return ctypes.POINTER(_MIRROR[base])
     if depth == 0:
-        raise VknLibraryError(f'include/vkn.h: {where}: {base!r} by value has no ctypes counterpart here')
+        raise VknLibraryError(f'{where}: {base!r} by value has no ctypes counterpart here')
     return ctypes.c_void_p
 
 
-for _name, _fields in STRUCTS.items():
-    MIRRORS[_name] = type(_name, (ctypes.Structure,), {
-        '__doc__': f'Mirror of include/vkn.h: {_name} (device pointers as integers).',
-        '_fields_': [(f, _ctype(b, d, _name) * n if n else _ctype(b, d, _name)) for f, b, d, n in _fields]})
-for _name, _fields in TRACK_TRAIN_STRUCTS.items():
-    TRACK_TRAIN_MIRRORS[_name] = type(_name, (ctypes.Structure,), {
-        '__doc__': f'Mirror of include/vkn_track_train.h: {_name}.',
-        '_fields_': [(f, _ctype(b, d, _name) * n if n else _ctype(b, d, _name)) for f, b, d, n in _fields]})
-globals().update(TRACK_TRAIN_MIRRORS)       # VknTrackLossCfg
-for _name, _fields in GT_STRUCTS.items():
-    GT_MIRRORS[_name] = type(_name, (ctypes.Structure,), {
-        '__doc__': f'Mirror of include/vkn_gt.h: {_name} (device pointers as integers).',
-        '_fields_': [(f, _ctype(b, d, _name) * n if n else _ctype(b, d, _name)) for f, b, d, n in _fields]})
-globals().update(GT_MIRRORS)                # VknGtImage
+for _h, _name, _fields in _each('structs'):
+    _at = f'include/{_h}: {_name}'
+    ABI[_h].mirrors[_name] = _MIRROR[_name] = type(_name, (ctypes.Structure,), {
+        '__doc__': f'Mirror of {_at} (device pointers as integers).',
+        '_fields_': [(f, _ctype(b, d, _at) * n if n else _ctype(b, d, _at)) for f, b, d, n in _fields]})
 # importable by name: VknDims, VknStageWeights, VknSplitItem, VknDwItem, VknUpdatorNorms, VknUpdatorNormGrads, VknPanopticCfg, VknAssignCfg,
-# VknAssignProblem, VknLsapProblem, VknTailImage, VknTailCfg, VknAdamwItem, VknTrackerCfg
-globals().update(MIRRORS)
+# VknAssignProblem, VknLsapProblem, VknTailImage, VknTailCfg, VknAdamwItem, VknTrackerCfg, VknTrackLossCfg, VknGtImage
+globals().update(_MIRROR)
 
 # The pointer parameters that do NOT follow _ctype's rule: (function, parameter) -> ctypes type.
 POINTER_EXCEPTIONS = {
@@ -171,9 +171,8 @@ POINTER_EXCEPTIONS = {
     ('vkn_sum_n_f32', 'srcs'): ctypes.POINTER(ctypes.c_void_p),                   # a HOST array of device pointers, (c_void_p * n)(...)
     ('vkn_qd_tracker_state_layout', 'offsets12'): ctypes.POINTER(ctypes.c_size_t),  # a HOST array the call fills, (c_size_t * 12)()
 }
-for _fn, _p in POINTER_EXCEPTIONS:
-    if _p not in [q[0] for q in PROTOS.get(_fn, ((), ()))[1]]:
-        raise VknLibraryError(f'POINTER_EXCEPTIONS names {_fn}({_p}), which include/vkn.h does not declare')
+for _fn, _p in set(POINTER_EXCEPTIONS) - {(fn, q[0]) for _, fn, (_, params) in _each('protos') for q in params}:
+    raise VknLibraryError(f'POINTER_EXCEPTIONS names {_fn}({_p}), which none of the headers {ABI_HEADERS} declares')
 
 DEBUG_LIBPATH = os.path.join(LIBDIR, 'libvkn_debug.so')
 
@@ -188,9 +187,9 @@ def _hipcc(args, verbose=False, what='hipcc'):
 
 
 def _shared_deps(debug):
-    """What every object depends on besides csrc/: the public header and, in the debug build, the kernel variants it #includes."""
+    """What every object depends on besides csrc/: the public headers and, in the debug build, the kernel variants it #includes."""
     exp = os.path.join(os.path.dirname(HERE), 'tools', 'experiments')
-    return [HEADER, TRACK_HEADER, TRACK_TRAIN_HEADER, GT_HEADER, DECODE_HEADER] + ([os.path.join(exp, f) for f in os.listdir(exp)] if debug and os.path.isdir(exp) else [])
+    return [h.path for h in ABI.values()] + ([os.path.join(exp, f) for f in os.listdir(exp)] if debug and os.path.isdir(exp) else [])
 
 
 def _stale(path=None):
@@ -258,7 +257,7 @@ def use_debug():
 
 
 def lib():
-    """The loaded library (ctypes.CDLL) with the header's prototypes set.  Raises VknLibraryError when it is not built."""
+    """The loaded library (ctypes.CDLL) with the headers' prototypes set.  Raises VknLibraryError when it is not built."""
     global _LIB
     if _LIB is not None:
         return _LIB
@@ -267,17 +266,17 @@ def lib():
         raise VknLibraryError(f'{path} is missing — run `python -c "import __graft_entry__ as g; g.build()"` '
                               '(there is deliberately no CPU fallback)')
     L = ctypes.CDLL(path)
-    for name, (result, params) in {**PROTOS, **TRACK_PROTOS, **TRACK_TRAIN_PROTOS, **GT_PROTOS, **DECODE_PROTOS}.items():
-        fn = getattr(L, name)
-        fn.restype = _ctype(*result, name, result=True)
-        fn.argtypes = [POINTER_EXCEPTIONS.get((name, p)) or _ctype(base, depth, name) for p, base, depth in params]
+    for h, name, (result, params) in _each('protos'):
+        fn, at = getattr(L, name), f'include/{h}: {name}'
+        fn.restype = _ctype(*result, at, result=True)
+        fn.argtypes = [POINTER_EXCEPTIONS.get((name, p)) or _ctype(base, depth, at) for p, base, depth in params]
     # header vs binary: structs are handed to the kernels verbatim, so a library built from another header means garbage pointers
-    for name, mirror in {**MIRRORS, **TRACK_TRAIN_MIRRORS, **GT_MIRRORS}.items():
+    for h, name, mirror in _each('mirrors'):
         probe = 'vkn_sizeof_' + re.sub(r'(?<!^)(?=[A-Z])', '_', name[3:]).lower()
-        if probe not in PROTOS and probe not in TRACK_TRAIN_PROTOS and probe not in GT_PROTOS:
-            raise VknLibraryError(f'include/vkn.h declares struct {name} without its size probe {probe}()')
+        if not any(probe in hdr.protos for hdr in ABI.values()):        # any header may declare a struct's size probe
+            raise VknLibraryError(f'include/{h} declares struct {name} without its size probe {probe}()')
         if getattr(L, probe)() != ctypes.sizeof(mirror):
-            raise VknLibraryError(f'{path} does not match include/vkn.h: struct {name} is {getattr(L, probe)()} bytes in the library, '
+            raise VknLibraryError(f'{path} does not match include/{h}: struct {name} is {getattr(L, probe)()} bytes in the library, '
                                   f'{ctypes.sizeof(mirror)} in the header')
     _LIB = L
     return L
