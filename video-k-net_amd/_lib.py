@@ -1,6 +1,7 @@
 """ctypes binding of libvkn.so, computed from its C ABI in the headers `ABI_HEADERS` under include/, + the hipcc build recipe.
 `ABI` maps each header to what its own text declares (prototypes, structs, constants, ctypes mirrors); a header is read once, knowing
 the headers it #includes, and no name may be declared twice.  `PROTOS`, `SYMBOLS`, `STRUCTS`, `MIRRORS` are include/vkn.h's part.
+`EXTENSION_HEADERS` / `ABI_EXT` is a second such table behind the first: extension parts, read in the same pass and bound by the same loops.
 
 The library is built IN-TREE (`video-k-net_amd/lib/libvkn.so`) so that it travels with the repo snapshot to the GPU
 box; there is no CPU fallback: if the library is missing every op raises `VknLibraryError`.
@@ -15,10 +16,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libvkn.so')
-SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_api.hip')
+SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_segloss.hip', 'vkn_api.hip')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 # The C ABI, one header per part, each behind the headers it #includes.  A new part is one more name here.
 ABI_HEADERS = ('vkn.h', 'vkn_track.h', 'vkn_track_train.h', 'vkn_gt.h', 'vkn_decode.h')
+# Extension parts: read, mirrored, bound and probed exactly as the headers above (after them, so they may #include any of those), but kept
+# in their own table `ABI_EXT`, and their constants in their own records, not in `CONSTS`: `ABI` / `CONSTS` stay what ABI_HEADERS declare.
+EXTENSION_HEADERS = ('vkn_seg_loss.h',)
 
 
 class VknLibraryError(RuntimeError):
@@ -122,14 +126,17 @@ def read_abi(include_dir, names):
     return abi
 
 
-def _each(field):
-    """[(header, name, value)] of one field of every header's record, in the headers' order"""
-    return [(h, k, v) for h, hdr in ABI.items() for k, v in getattr(hdr, field).items()]
+def _each(field, tables=None):
+    """[(header, name, value)] of one field of every header's record — `ABI`'s, then `ABI_EXT`'s — in the headers' order"""
+    return [(h, k, v) for t in (tables or (ABI, ABI_EXT)) for h, hdr in t.items() for k, v in getattr(hdr, field).items()]
 
 
-ABI = read_abi(INCLUDE, ABI_HEADERS)
+_ALL = read_abi(INCLUDE, ABI_HEADERS + EXTENSION_HEADERS)          # ONE reading: includes resolve, a name declared twice is an error
+ABI = {h: _ALL[h] for h in ABI_HEADERS}
+ABI_EXT = {h: _ALL[h] for h in EXTENSION_HEADERS}
 HEADER, PROTOS, SYMBOLS, STRUCTS, MIRRORS = (getattr(ABI['vkn.h'], k) for k in ('path', 'protos', 'symbols', 'structs', 'mirrors'))
-CONSTS = {k: v for _, k, v in _each('consts')}      # every header's constants: no name is declared twice
+CONSTS = {k: v for _, k, v in _each('consts', (ABI,))}      # every ABI header's constants: no name is declared twice
+SEG = ABI_EXT['vkn_seg_loss.h'].consts              # an extension's constants stay in its own record
 GT_MAX_IMAGES = CONSTS['VKN_GT_MAX_IMAGES']
 GT_MAX_CLASSES = CONSTS['VKN_GT_MAX_CLASSES']
 GT_MAX_IDS = CONSTS['VKN_GT_MAX_IDS']
@@ -158,11 +165,11 @@ def _ctype(base, depth, where, result=False):
 
 for _h, _name, _fields in _each('structs'):
     _at = f'include/{_h}: {_name}'
-    ABI[_h].mirrors[_name] = _MIRROR[_name] = type(_name, (ctypes.Structure,), {
+    _ALL[_h].mirrors[_name] = _MIRROR[_name] = type(_name, (ctypes.Structure,), {
         '__doc__': f'Mirror of {_at} (device pointers as integers).',
         '_fields_': [(f, _ctype(b, d, _at) * n if n else _ctype(b, d, _at)) for f, b, d, n in _fields]})
 # importable by name: VknDims, VknStageWeights, VknSplitItem, VknDwItem, VknUpdatorNorms, VknUpdatorNormGrads, VknPanopticCfg, VknAssignCfg,
-# VknAssignProblem, VknLsapProblem, VknTailImage, VknTailCfg, VknAdamwItem, VknTrackerCfg, VknTrackLossCfg, VknGtImage
+# VknAssignProblem, VknLsapProblem, VknTailImage, VknTailCfg, VknAdamwItem, VknTrackerCfg, VknTrackLossCfg, VknGtImage, VknSegImage
 globals().update(_MIRROR)
 
 # The pointer parameters that do NOT follow _ctype's rule: (function, parameter) -> ctypes type.
@@ -172,7 +179,7 @@ POINTER_EXCEPTIONS = {
     ('vkn_qd_tracker_state_layout', 'offsets12'): ctypes.POINTER(ctypes.c_size_t),  # a HOST array the call fills, (c_size_t * 12)()
 }
 for _fn, _p in set(POINTER_EXCEPTIONS) - {(fn, q[0]) for _, fn, (_, params) in _each('protos') for q in params}:
-    raise VknLibraryError(f'POINTER_EXCEPTIONS names {_fn}({_p}), which none of the headers {ABI_HEADERS} declares')
+    raise VknLibraryError(f'POINTER_EXCEPTIONS names {_fn}({_p}), which none of the headers {ABI_HEADERS + EXTENSION_HEADERS} declares')
 
 DEBUG_LIBPATH = os.path.join(LIBDIR, 'libvkn_debug.so')
 
@@ -189,7 +196,7 @@ def _hipcc(args, verbose=False, what='hipcc'):
 def _shared_deps(debug):
     """What every object depends on besides csrc/: the public headers and, in the debug build, the kernel variants it #includes."""
     exp = os.path.join(os.path.dirname(HERE), 'tools', 'experiments')
-    return [h.path for h in ABI.values()] + ([os.path.join(exp, f) for f in os.listdir(exp)] if debug and os.path.isdir(exp) else [])
+    return [h.path for h in _ALL.values()] + ([os.path.join(exp, f) for f in os.listdir(exp)] if debug and os.path.isdir(exp) else [])
 
 
 def _stale(path=None):
@@ -273,7 +280,7 @@ def lib():
     # header vs binary: structs are handed to the kernels verbatim, so a library built from another header means garbage pointers
     for h, name, mirror in _each('mirrors'):
         probe = 'vkn_sizeof_' + re.sub(r'(?<!^)(?=[A-Z])', '_', name[3:]).lower()
-        if not any(probe in hdr.protos for hdr in ABI.values()):        # any header may declare a struct's size probe
+        if not any(probe in hdr.protos for hdr in _ALL.values()):        # any header may declare a struct's size probe
             raise VknLibraryError(f'include/{h} declares struct {name} without its size probe {probe}()')
         if getattr(L, probe)() != ctypes.sizeof(mirror):
             raise VknLibraryError(f'{path} does not match include/{h}: struct {name} is {getattr(L, probe)()} bytes in the library, '

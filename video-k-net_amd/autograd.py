@@ -391,3 +391,29 @@ def lazy_upsample(x, values, stride):
     out = LazyUpsampleFn.apply(x, values, stride)
     out._vkn_lowres = x          # (kernel_iter_head._train_stages: these values belong to exactly this low-res tensor)
     return out
+
+
+class SegLossFn(torch.autograd.Function):
+    """`loss_rpn_seg` of the kernel-initialisation head from the LOW-RES semantic logits and the one-byte target map (include/
+    vkn_seg_loss.h): two launches forward, one backward (csrc/vkn_segloss.hip); neither the up-scaled logits nor their gradient exist.
+    The upstream gradient travels as a device scalar, nothing reads the host: capturable.  `tgt` and `dense_pos` carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, low, tgt, dense_pos, mode, stride, alpha, gamma, loss_weight):
+        low = low.contiguous()
+        loss, state = ops.seg_loss_fwd(low, tgt, dense_pos, mode, stride, alpha, gamma, loss_weight)
+        ctx.save_for_backward(low, tgt, state)
+        ctx.args = (mode, stride, alpha, gamma)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        low, tgt, state = ctx.saved_tensors
+        mode, stride, alpha, gamma = ctx.args
+        return ops.seg_loss_bwd(low, tgt, g.reshape(1).float(), state, mode, stride, alpha, gamma), None, None, None, None, None, None, None
+
+
+def seg_loss(low, tgt, dense_pos, mode, stride, alpha=0.25, gamma=2.0, loss_weight=1.0):
+    """low fp32 [B,ncls,h,w]; tgt uint8 [B,S h,S w] and dense_pos int32 [1] of `ops.seg_targets`; mode `ops.SEG_LOSS_FOCAL` / `_CE`
+    -> the loss as a 0-d tensor."""
+    return SegLossFn.apply(low, tgt, dense_pos, mode, stride, alpha, gamma, loss_weight)

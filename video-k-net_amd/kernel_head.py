@@ -39,6 +39,10 @@ class _ConvGNReLU(nn.Module):
 
 @register_head
 class ConvKernelHead(nn.Module):
+    # True: `forward_train` takes `loss_rpn_seg` from `SegLossTail` (seg_tail.py) — the semantic logits are not up-scaled and
+    # `seg_targets` is not painted in torch.  Same loss up to the order of the fp32 sums; everything else runs as before.
+    fused_seg_loss = False
+    _seg_tail_allowed = True        # (the VIS head below keeps the composition whatever the flag says)
 
     def __init__(self, num_proposals=100, in_channels=256, out_channels=256, num_heads=8, num_cls_fcs=1, num_seg_convs=1,
                  num_loc_convs=1, att_dropout=False, localization_fpn=None, conv_kernel_size=1,
@@ -247,20 +251,24 @@ class ConvKernelHead(nn.Module):
         num_imgs = len(img_metas)
         proposal_feats, x_feats, mask_preds, cls_scores, seg_preds = self._decode_init_proposals(img, img_metas)
         s_ = self.feat_downsample_stride
+        seg_tail = self._seg_tail() if self.fused_seg_loss and self._seg_tail_allowed and seg_preds is not None else None
         if s_ > 1:
             scaled_mask_preds = F.interpolate(mask_preds, scale_factor=s_, mode='bilinear', align_corners=False)
             scaled_seg_preds = (F.interpolate(seg_preds, scale_factor=s_, mode='bilinear', align_corners=False)
-                                if seg_preds is not None else None)
+                                if seg_preds is not None and seg_tail is None else None)
         else:
-            scaled_mask_preds, scaled_seg_preds = mask_preds, seg_preds
+            scaled_mask_preds, scaled_seg_preds = mask_preds, (seg_preds if seg_tail is None else None)
         if self.hard_target:
             gt_masks = [g.bool().float() for g in gt_masks]
-        sampling_results = []
+        sampling_results, assign_results = [], []
         for i in range(num_imgs):
             assign_result = self.assigner.assign(scaled_mask_preds[i].detach(), None, gt_masks[i], gt_labels[i], img_metas[i])
+            assign_results.append(assign_result)
             sampling_results.append(self.sampler.sample(assign_result, scaled_mask_preds[i], gt_masks[i]))
-        mask_targets = self._targets(sampling_results, self.train_cfg, True, gt_sem_seg, gt_sem_cls)
+        mask_targets = self._targets(sampling_results, self.train_cfg, True, gt_sem_seg, gt_sem_cls, with_seg=seg_tail is None)
         losses = self.loss(scaled_mask_preds, cls_scores, scaled_seg_preds, proposal_feats, *mask_targets)
+        if seg_tail is not None:       # (`loss` skipped the branch: it was handed no up-scaled semantic logits)
+            losses['loss_rpn_seg'] = seg_tail.loss(seg_preds, seg_tail.targets(gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, assign_results))
         if hasattr(self.assigner, 'check_status'):
             self.assigner.check_status(wait=False)     # device LSAP status words -> the asynchronous flag queue (no stall)
         if self.cat_stuff_mask and self.training:
@@ -268,6 +276,14 @@ class ConvKernelHead(nn.Module):
             stuff_kernels = self.conv_seg.weight[self.num_thing_classes:].clone()
             proposal_feats = torch.cat([proposal_feats, stuff_kernels[None].expand(num_imgs, *stuff_kernels.size())], dim=1)
         return losses, proposal_feats, x_feats, mask_preds, cls_scores
+
+    def _seg_tail(self):
+        """the `SegLossTail` of this head's `loss_seg` (built once; it decides per call whether its kernels apply)"""
+        tail = getattr(self, '_seg_tail_obj', None)
+        if tail is None or tail.loss_seg is not self.loss_seg:
+            from .seg_tail import SegLossTail
+            tail = self._seg_tail_obj = SegLossTail(self.num_classes, self.feat_downsample_stride, self.loss_seg)
+        return tail
 
     def loss(self, mask_pred, cls_scores, seg_preds, proposal_feats, labels, label_weights, mask_targets, mask_weights, seg_targets,
              reduction_override=None, **kwargs):
@@ -313,14 +329,15 @@ class ConvKernelHead(nn.Module):
                 losses['loss_rpn_seg'] = self.loss_seg(flat, tgt, ignore_index=self.num_classes)
         return losses
 
-    def _image_targets(self, n, shape, dtype, dev, pos_inds, pos_gt_mask, pos_gt_labels, gt_sem_seg, gt_sem_cls, cfg):
+    def _image_targets(self, n, shape, dtype, dev, pos_inds, pos_gt_mask, pos_gt_labels, gt_sem_seg, gt_sem_cls, cfg, with_seg=True):
         """Targets of one image (reference :427-466) from what defines them — the matched rows with their ground truth — without the
         matched / unmatched mask copies the reference passes around:
           labels [n] (background = num_classes), label_weights [n] (matched: pos_weight if > 0, everything else 1),
           mask_targets [n, H, W] and mask_weights (1 on the matched rows; an expanded view of a [n] vector),
           seg_targets [H, W]: the dense semantic target.  The reference PAINTS it — the stuff masks in order, then every matched
           instance's label over its mask in sample order — so a pixel ends up with the label of the LAST layer covering it; here
-          that is one masked arg-max over the stacked layers (no per-instance boolean-mask writes, each of which synchronises)."""
+          that is one masked arg-max over the stacked layers (no per-instance boolean-mask writes, each of which synchronises).
+          `with_seg=False` (the fused semantic loss paints its own map): None."""
         H, W = shape
         k = int(pos_inds.shape[0])
         labels = torch.full((n,), self.num_classes, dtype=torch.long, device=dev)
@@ -328,7 +345,7 @@ class ConvKernelHead(nn.Module):
         mask_targets = torch.zeros((n, H, W), dtype=dtype, device=dev)
         row_w = torch.zeros((n,), dtype=dtype, device=dev)
         layers, layer_labels = [], []
-        if gt_sem_cls is not None and gt_sem_seg is not None and len(gt_sem_cls) > 0:
+        if with_seg and gt_sem_cls is not None and gt_sem_seg is not None and len(gt_sem_cls) > 0:
             layers.append(gt_sem_seg.to(dev).bool())
             layer_labels.append(gt_sem_cls.to(dev).long())
         if k > 0:
@@ -338,9 +355,12 @@ class ConvKernelHead(nn.Module):
                 label_weights.index_fill_(0, pos_inds, float(pw))
             mask_targets[pos_inds] = pos_gt_mask.to(dtype)
             row_w.index_fill_(0, pos_inds, 1.0)
-            layers.append(pos_gt_mask.bool())
-            layer_labels.append(pos_gt_labels.long())
-        if layers:
+            if with_seg:
+                layers.append(pos_gt_mask.bool())
+                layer_labels.append(pos_gt_labels.long())
+        if not with_seg:
+            seg_targets = None
+        elif layers:
             stack, lab = torch.cat(layers), torch.cat(layer_labels)
             order = torch.arange(stack.shape[0], device=dev, dtype=torch.int32).view(-1, 1, 1)
             top = torch.where(stack, order, order.new_full((), -1)).amax(dim=0).long()
@@ -358,17 +378,17 @@ class ConvKernelHead(nn.Module):
         """:468-504 (`gt_mask` is not read there either: the sampling results carry the matched ground truth)"""
         return self._targets(sampling_results, rpn_train_cfg, concat, gt_sem_seg, gt_sem_cls)
 
-    def _targets(self, sampling_results, rpn_train_cfg, concat, gt_sem_seg, gt_sem_cls):
+    def _targets(self, sampling_results, rpn_train_cfg, concat, gt_sem_seg, gt_sem_cls, with_seg=True):
         n = len(sampling_results)
         if gt_sem_seg is None:
             gt_sem_seg, gt_sem_cls = [None] * n, [None] * n      # (the reference hard-codes 2, :480-481)
-        out = [self._image_targets(r.num_pos + r.num_neg, r.mask_shape[-2:], r.mask_dtype, r.device, r.pos_inds, r.pos_gt_masks, r.pos_gt_labels, gt_sem_seg[i], gt_sem_cls[i], rpn_train_cfg)
+        out = [self._image_targets(r.num_pos + r.num_neg, r.mask_shape[-2:], r.mask_dtype, r.device, r.pos_inds, r.pos_gt_masks, r.pos_gt_labels, gt_sem_seg[i], gt_sem_cls[i], rpn_train_cfg, with_seg)
                for i, r in enumerate(sampling_results)]
         labels, label_weights, mask_targets, mask_weights, seg_targets = (list(t) for t in zip(*out))
         if concat:
             labels, label_weights = torch.cat(labels, 0), torch.cat(label_weights, 0)
             mask_targets, mask_weights = torch.cat(mask_targets, 0), torch.cat(mask_weights, 0)
-            seg_targets = torch.stack(seg_targets, 0)
+            seg_targets = torch.stack(seg_targets, 0) if with_seg else None
         return labels, label_weights, mask_targets, mask_weights, seg_targets
 
 
@@ -380,6 +400,7 @@ class ConvKernelHeadVideo(ConvKernelHead):
     differs from the per-image head is bookkeeping only — per-frame metas come as `ref_img_metas[clip][frame]`, ground-truth masks
     as `gt_masks[clip][frame]` and labels as `gt_labels[clip]` rows `(frame index, label)` (:303-317).  So the frames are
     flattened here and everything — HIP kernel-init pass, assignment, targets, losses — is the base class's."""
+    _seg_tail_allowed = False       # `fused_seg_loss` is the per-image head's: this head's `forward_train` keeps its own path
 
     def _init_layers(self):
         super()._init_layers()

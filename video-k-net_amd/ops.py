@@ -947,6 +947,106 @@ def gt_match_indices(key_ids, ref_ids):
     return match, off
 
 
+# ---- the dense semantic loss of the kernel-initialisation head from the low-res logits (include/vkn_seg_loss.h)
+_SEG = _lib.SEG
+SEG_LOSS_FOCAL, SEG_LOSS_CE = _SEG['VKN_SEG_LOSS_FOCAL'], _SEG['VKN_SEG_LOSS_CE']
+SEG_MAX_IMAGES, SEG_MAX_CLASSES, SEG_MAX_ROWS = _SEG['VKN_SEG_MAX_IMAGES'], _SEG['VKN_SEG_MAX_CLASSES'], _SEG['VKN_SEG_MAX_ROWS']
+
+
+def seg_loss_supported(B, ncls, h, w, stride):
+    """The envelope of `seg_targets` / `seg_loss_fwd` / `seg_loss_bwd` (include/vkn_seg_loss.h) as far as shapes decide it."""
+    return (stride in (1, 2, 4) and 1 <= ncls <= SEG_MAX_CLASSES and 1 <= B <= SEG_MAX_IMAGES and h >= 1 and w >= 1
+            and ncls * h * w * 4 < 2 ** 31 and stride * stride * h * w < 2 ** 31 and h <= 3 * 65535 and stride * h <= 4 * 65535)     # the last two: the grids of the backward / the targets
+
+
+def _req_plain(t, name, dtype):
+    """contiguous CUDA tensor of `dtype`, wherever it starts: views into a bank are taken as they are (4 / 8-byte alignment is theirs)"""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.VknLibraryError(f'{name}: expected a CUDA/HIP tensor — the MI355X path has no CPU fallback')
+    if t.dtype != dtype:
+        raise TypeError(f'{name}: expected {dtype}, got {t.dtype}')
+    return t.contiguous()
+
+
+def seg_targets(gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_inds, num_classes, shape, tgt=None, status=None):
+    """The painted dense target map of B images in one launch (vkn_seg_targets_u8): per image gt_masks fp32 [G_b,H,W], gt_labels int64
+    [G_b], gt_sem_seg fp32 [n_b,H,W] / gt_sem_cls int64 [n_b] (or None for both lists / entries: no stuff layer) and gt_inds int64 [Np]
+    (the assigner's: 0 = unmatched).  shape = (H, W).  -> (tgt uint8 [B,H,W], dense_pos int32 [1]); `tgt`: write into this tensor;
+    `status`: the int32 status word to use (default: this stream's, `workspace_status`).  Nothing here synchronises; the tensors named
+    in the per-image array are kept alive by the caller until the stream has run the launch (they are the step's ground truth)."""
+    B, (H, W) = len(gt_masks), (int(v) for v in shape)
+    if not (len(gt_labels) == len(gt_inds) == B) or B == 0:
+        raise ValueError('seg_targets: one mask, label and gt_inds tensor per image')
+    imgs = (_lib.VknSegImage * B)()
+    keep = []
+    dev = gt_inds[0].device
+    for b in range(B):
+        gi = _req_plain(gt_inds[b].reshape(-1), 'gt_inds', torch.int64)
+        G = int(gt_masks[b].shape[0]) if gt_masks[b] is not None else 0
+        m = lab = s = sc = None
+        if G:
+            m, lab = _req_plain(gt_masks[b], 'gt_masks', torch.float32), _req_plain(gt_labels[b].reshape(-1), 'gt_labels', torch.int64)
+            if tuple(m.shape[1:]) != (H, W) or lab.numel() != G:
+                raise ValueError(f'seg_targets: gt_masks[{b}] must be [G, {H}, {W}] with G labels')
+        ns = 0
+        if gt_sem_seg is not None and gt_sem_cls is not None and gt_sem_seg[b] is not None and gt_sem_cls[b] is not None:
+            ns = int(gt_sem_cls[b].numel())
+        if ns:
+            s, sc = _req_plain(gt_sem_seg[b], 'gt_sem_seg', torch.float32), _req_plain(gt_sem_cls[b].reshape(-1), 'gt_sem_cls', torch.int64)
+            if tuple(s.shape) != (ns, H, W):
+                raise ValueError(f'seg_targets: gt_sem_seg[{b}] must be [{ns}, {H}, {W}]')
+        keep += [gi, m, lab, s, sc]
+        imgs[b] = _lib.VknSegImage(m.data_ptr() if G else None, s.data_ptr() if ns else None, lab.data_ptr() if G else None,
+                                   sc.data_ptr() if ns else None, gi.data_ptr() if gi.numel() else None, G, ns, int(gi.numel()))
+    if tgt is None:
+        tgt = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    elif tuple(tgt.shape) != (B, H, W) or tgt.dtype != torch.uint8 or not tgt.is_contiguous() or not tgt.is_cuda:
+        raise ValueError(f'seg_targets: tgt must be a contiguous CUDA uint8 [{B}, {H}, {W}]')
+    dense_pos = torch.empty((1,), dtype=torch.int32, device=dev)
+    if status is None:
+        status = _workspace(256, dev)          # the header of this stream's workspace: its first word is the status word
+    with torch.cuda.device(dev):
+        check(_lib.lib().vkn_seg_targets_u8(imgs, B, H, W, int(num_classes), _ptr(tgt), _ptr(dense_pos), _ptr(status), _stream()))
+    return tgt, dense_pos
+
+
+def seg_loss_fwd(low, tgt, dense_pos, mode, stride, alpha=0.25, gamma=2.0, loss_weight=1.0):
+    """`loss_rpn_seg` from the low-res logits (vkn_seg_loss_fwd_f32).  low fp32 [B,ncls,h,w]; tgt uint8 [B,S h,S w] and dense_pos int32
+    [1] as `seg_targets` returns them; mode SEG_LOSS_FOCAL / SEG_LOSS_CE.  -> (loss fp32 0-d, state): `state` is what `seg_loss_bwd`
+    reads, a tensor of its own so that it survives until the backward."""
+    low = _req_plain(low, 'low', torch.float32)
+    B, ncls, h, w = (int(v) for v in low.shape)
+    S = int(stride)
+    tgt = _req_plain(tgt, 'tgt', torch.uint8)
+    if tuple(tgt.shape) != (B, S * h, S * w):
+        raise ValueError(f'seg_loss_fwd: tgt must be [{B}, {S * h}, {S * w}], got {tuple(tgt.shape)}')
+    dp = _req_plain(dense_pos, 'dense_pos', torch.int32) if dense_pos is not None else None
+    L = _lib.lib()
+    loss = torch.empty((), dtype=torch.float32, device=low.device)
+    state = torch.empty((max(L.vkn_seg_loss_state_bytes(int(mode), B, h, w, S), 64),), dtype=torch.uint8, device=low.device)
+    with torch.cuda.device(low.device):
+        check(L.vkn_seg_loss_fwd_f32(_ptr(low), _ptr(tgt), _ptr(dp), int(mode), B, ncls, h, w, S, float(alpha), float(gamma),
+                                     float(loss_weight), _ptr(loss), _ptr(state), _stream()))
+    return loss, state
+
+
+def seg_loss_bwd(low, tgt, gout, state, mode, stride, alpha=0.25, gamma=2.0, grad_low=None):
+    """gout x d loss / d low (vkn_seg_loss_bwd_f32).  gout: DEVICE fp32 scalar; state: the forward's.  -> grad_low fp32 [B,ncls,h,w]
+    (`grad_low`: write into this contiguous tensor), every element written once."""
+    low, tgt, g = _req_plain(low, 'low', torch.float32), _req_plain(tgt, 'tgt', torch.uint8), _req_plain(gout.reshape(-1), 'gout', torch.float32)
+    B, ncls, h, w = (int(v) for v in low.shape)
+    if g.numel() != 1:
+        raise ValueError('gout must hold the one upstream gradient')
+    if grad_low is None:
+        grad_low = torch.empty_like(low)
+    elif grad_low.shape != low.shape or grad_low.dtype != torch.float32 or not grad_low.is_contiguous() or not grad_low.is_cuda:
+        raise ValueError('seg_loss_bwd: grad_low must be a contiguous CUDA fp32 tensor of the shape of low')
+    with torch.cuda.device(low.device):
+        check(_lib.lib().vkn_seg_loss_bwd_f32(_ptr(low), _ptr(tgt), _ptr(g), int(mode), B, ncls, h, w, int(stride), float(alpha), float(gamma),
+                                              _ptr(state), _ptr(grad_low), _stream()))
+    return grad_low
+
+
 def panoptic_thing_first(thing_masks, thing_scores, thing_labels, thing_order, stuff_masks, stuff_labels, stuff_order,
                          instance_score_thr, iou_thr, stuff_max_area):
     """Thing-first panoptic merge of ONE image on the device (`merge_stuff_thing`, knet/det/kernel_iter_head.py:385-465).
