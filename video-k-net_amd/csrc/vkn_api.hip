@@ -1003,7 +1003,7 @@ int vkn_mask_gather_f32(const float* x, const float* mask_logits, float thr_logi
     if (!x || !mask_logits || !xraw_out || B <= 0 || N <= 0 || C <= 0 || P <= 0) return VKN_E_ARG;
     if (!aligned16(x) || !aligned16(mask_logits) || !aligned16(xraw_out)) return VKN_E_ALIGN;
     if (C % 32 != 0 || C > 256 || N > 256) return VKN_E_SHAPE;
-    if (!ws || ws_bytes < vkn_gather_workspace_bytes(B, N, C, P)) return VKN_E_WORKSPACE;
+    if (!ws || ws_bytes < vkn_gather_workspace_bytes(B, N, C, P) || !aligned16(ws)) return VKN_E_WORKSPACE;
     GatherWs g;
     carve_gather(B, N, C, P, static_cast<char*>(ws), &g);
     float* cnt = cnt_out ? cnt_out : g.cnt;
@@ -1020,7 +1020,7 @@ int vkn_mask_gather_real_f32(const float* x, const float* a, float* out, float* 
     if (!x || !a || !out || B <= 0 || N <= 0 || C <= 0 || P <= 0) return VKN_E_ARG;
     if (!aligned16(x) || !aligned16(a) || !aligned16(out)) return VKN_E_ALIGN;
     if (C % 32 != 0 || C > 256 || N > 256) return VKN_E_SHAPE;
-    if (!ws || ws_bytes < vkn_gather_workspace_bytes(B, N, C, P)) return VKN_E_WORKSPACE;
+    if (!ws || ws_bytes < vkn_gather_workspace_bytes(B, N, C, P) || !aligned16(ws)) return VKN_E_WORKSPACE;
     GatherWs g;
     carve_gather(B, N, C, P, static_cast<char*>(ws), &g);
     return vkn_launch_gather_real(x, a, out, asum_out ? asum_out : g.cnt, g.part, g.cntp, B, N, C, P, N, static_cast<hipStream_t>(stream));
@@ -1042,7 +1042,7 @@ int vkn_mask_decode_f32(const float* x, const float* kernels, const float* bias,
         if (xdt_of(flags)) return VKN_E_SHAPE;
         return vkn_launch_decode_ref(x, kernels, bias, out, B, N, C, P, st);
     }
-    if (!ws || ws_bytes < vkn_decode_workspace_bytes(B, N, C)) return VKN_E_WORKSPACE;
+    if (!ws || ws_bytes < vkn_decode_workspace_bytes(B, N, C) || !aligned16(ws)) return VKN_E_WORKSPACE;
     _Float16 *kfh, *kfl;
     carve_planes(B, N, C, static_cast<char*>(ws), &kfh, &kfl);
     VKN_TRY(vkn_launch_split_planes(kernels, kfh, kfl, B, N, C, st));
@@ -1055,7 +1055,7 @@ int vkn_mask_decode_scaled_f32(const float* x, const float* kernels, const float
     if (!aligned16(x) || !aligned16(kernels) || !aligned16(out)) return VKN_E_ALIGN;
     if (C % 32 != 0 || C > 256 || N > 256) return VKN_E_SHAPE;
     if ((flags & VKN_FLAG_REF_KERNELS) || (P & 1)) return VKN_E_SHAPE;
-    if (!ws || ws_bytes < vkn_decode_workspace_bytes(B, N, C)) return VKN_E_WORKSPACE;
+    if (!ws || ws_bytes < vkn_decode_workspace_bytes(B, N, C) || !aligned16(ws)) return VKN_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     _Float16 *kfh, *kfl;
     carve_planes(B, N, C, static_cast<char*>(ws), &kfh, &kfl);
@@ -1118,7 +1118,7 @@ int vkn_decode_gather_x(const void* xv, int x_dtype, const void* kf_hi, const vo
     if (!x || !kf_hi || !kf_lo || !xraw_out || !cnt_out || B <= 0 || N <= 0 || C <= 0 || P <= 0) return VKN_E_ARG;
     if (!aligned16(x) || !aligned16(kf_hi) || !aligned16(kf_lo) || !aligned16(xraw_out)) return VKN_E_ALIGN;
     if (N > 256 || !vkn_fused_supported(C, P)) return VKN_E_SHAPE;
-    if (!ws || ws_bytes < vkn_gather_workspace_bytes(B, N, C, P)) return VKN_E_WORKSPACE;
+    if (!ws || ws_bytes < vkn_gather_workspace_bytes(B, N, C, P) || !aligned16(ws)) return VKN_E_WORKSPACE;
     GatherWs g;
     carve_gather(B, N, C, P, static_cast<char*>(ws), &g);
     return vkn_launch_fused_decode_gather(x, static_cast<const _Float16*>(kf_hi), static_cast<const _Float16*>(kf_lo), bias,
@@ -1343,7 +1343,7 @@ int vkn_linear_f32(const float* A, const float* W, const void* w_split, const fl
                    int act, int ksplit, void* ws, size_t ws_bytes, void* stream) {
     if (!A || !W || !out || M <= 0 || K <= 0 || Nout <= 0) return VKN_E_ARG;
     if (K % 32 != 0) return VKN_E_SHAPE;
-    if (ksplit > 1 && (!ws || ws_bytes < (size_t)ksplit * M * Nout * sizeof(float))) return VKN_E_WORKSPACE;
+    if (ksplit > 1 && (!ws || ws_bytes < (size_t)ksplit * M * Nout * sizeof(float) || !aligned16(ws))) return VKN_E_WORKSPACE;
     if (w_split && K == 256 && ksplit <= 1 && M <= 32 * VKN_KS_MAX_ROW_TILES && aligned16(A) && aligned16(out) &&
         act >= 0 && act <= 2) {
         // up to 512 rows (the training chain at 1 - 4 frames per step): the column-spread phase kernel of the few-row chain as a

@@ -393,12 +393,13 @@ size_t vkn_conv_gn_workspace_bytes(int B, int Cout, int H, int W, int stride, in
 int vkn_conv_gn_f32(const float* x, const float* pos, const float* in_stats, const float* in_gamma, const float* in_beta, int in_groups,
                     int upsample, const void* wimg, int ksize, int stride, int groups, float* out, float* out_stats, int B, int Cin,
                     int H, int W, int Cout, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !wimg || !out || !out_stats || !ws) return VKN_E_ARG;
+    if (!x || !wimg || !out || !out_stats) return VKN_E_ARG;
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return VKN_E_ARG;
     if (Cin % 32 || Cout % 32 || Cin > 512 || Cout > 512 || (ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) ||
         (ksize == 1 && stride != 1) || groups <= 0 || Cout % groups || (upsample && !in_stats) || (in_stats && pos) ||
         (in_stats && (!in_gamma || !in_beta || in_groups <= 0 || Cin % in_groups)))
         return VKN_E_SHAPE;
+    if (!ws) return VKN_E_WORKSPACE;   // (include/vkn.h: a workspace that is NULL is VKN_E_WORKSPACE, as one that is too small)
     if (!fpn_aligned(x) || !fpn_aligned(out) || !fpn_aligned(wimg) || !fpn_aligned(ws)) return VKN_E_ALIGN;
     const size_t need = vkn_conv_gn_workspace_bytes(B, Cout, H, W, stride, upsample);
     if (ws_bytes < need) return VKN_E_WORKSPACE;
@@ -463,13 +464,14 @@ int vkn_localization_fpn_f32(const float* p2, const float* p3, const float* p4, 
                              const void* const* wimg, const float* const* gamma, const float* const* beta, int groups, float* loc,
                              float* sem, int B, int C, int H2, int W2, int H3, int W3, int H4, int W4, int H5, int W5, void* ws,
                              size_t ws_bytes, void* stream) {
-    if (!p2 || !p3 || !p4 || !p5 || !wimg || !gamma || !beta || !loc || !sem || !ws) return VKN_E_ARG;
+    if (!p2 || !p3 || !p4 || !p5 || !wimg || !gamma || !beta || !loc || !sem) return VKN_E_ARG;
     if (B <= 0 || C <= 0) return VKN_E_ARG;
     if (C % 32 || C > 256 || groups <= 0 || C % groups || !fpn_shapes_ok(H2, W2, H3, W3, H4, W4, H5, W5)) return VKN_E_SHAPE;
     const bool with_ls = wimg[8] != nullptr;
     for (int i = 0; i < (with_ls ? 10 : 8); ++i)
         if (!wimg[i] || !gamma[i] || !beta[i] || !fpn_aligned(wimg[i])) return VKN_E_ARG;
     if (with_ls != (wimg[9] != nullptr)) return VKN_E_ARG;
+    if (!ws) return VKN_E_WORKSPACE;
     for (const void* p : {(const void*)p2, (const void*)p3, (const void*)p4, (const void*)p5, (const void*)loc, (const void*)sem, (const void*)ws})
         if (!fpn_aligned(p)) return VKN_E_ALIGN;
     FpnWs w;

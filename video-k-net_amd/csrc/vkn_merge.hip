@@ -95,7 +95,7 @@ int vkn_panoptic_thing_first_u8(const unsigned char* thing_masks, const float* t
     if (Kt + Ks > 0 && !info) return VKN_E_ARG;                                            // no step, no row: a [0][5] table has no address
     if (Kt > 0 && (!thing_masks || !thing_scores || !thing_labels || !thing_order)) return VKN_E_ARG;
     if (Ks > 0 && (!stuff_masks || !stuff_labels || !stuff_order)) return VKN_E_ARG;
-    if (!ws || ws_bytes < vkn_merge_workspace_bytes(Kt, Ks)) return VKN_E_WORKSPACE;
+    if (!ws || ws_bytes < vkn_merge_workspace_bytes(Kt, Ks) || (reinterpret_cast<uintptr_t>(ws) & 15)) return VKN_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t steps = (size_t)Kt + Ks;
     unsigned* cnt = static_cast<unsigned*>(ws);
