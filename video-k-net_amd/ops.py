@@ -1485,3 +1485,51 @@ def localization_fpn(p2, p3, p4, p5, pos5, images, gammas, betas, groups):
         check(L.vkn_localization_fpn_f32(*[_ptr(p) for p in ps], _ptr(pos), arr(images), arr(gs), arr(bs), int(groups),
                                          _ptr(loc), _ptr(sem), B, C, *dims, _ptr(ws), ws.numel(), _stream()))
     return loc, sem
+
+
+# ---- the STQ meter (include/vkn_stq.h): one caller-owned state per sequence
+def stq_cfg(num_classes, ignore_label, label_bit_shift, offset, drop_ignored_gt=True, cap_gt=2048, cap_pred=8192, cap_pair=32768):
+    """The `VknStqCfg` of a meter; raises VknError (VKN_E_SHAPE) outside the envelope of include/vkn_stq.h."""
+    cfg = _lib.VknStqCfg(int(offset), int(num_classes), int(ignore_label), int(label_bit_shift), int(bool(drop_ignored_gt)), int(cap_gt),
+                         int(cap_pred), int(cap_pair))
+    if not _lib.lib().vkn_stq_state_bytes(ctypes.byref(cfg)):
+        raise _lib.VknError(-2, 'stq_cfg: outside the envelope of include/vkn_stq.h (classes 1..255, shift 1..30, offset >= classes << shift, '
+                                '((classes + 1) << shift) * offset < 2^62, capacities powers of two in [16, 2^20])')
+    return cfg
+
+
+def stq_layout(cfg):
+    """(state bytes, the eight byte offsets: header, confusion, gt keys, gt counts, pred keys, pred counts, pair keys, pair counts)"""
+    off = (ctypes.c_size_t * 8)()
+    check(_lib.lib().vkn_stq_state_layout(ctypes.byref(cfg), off))
+    return int(_lib.lib().vkn_stq_state_bytes(ctypes.byref(cfg))), [int(o) for o in off]
+
+
+def stq_state(cfg, device):
+    """A freshly reset state of one sequence: uint8 [vkn_stq_state_bytes] on `device`."""
+    state = torch.empty((stq_layout(cfg)[0],), dtype=torch.uint8, device=device)
+    return stq_reset(cfg, state)
+
+
+def stq_reset(cfg, state):
+    """Empty the state (vkn_stq_reset, one fill launch); returns it."""
+    with torch.cuda.device(state.device):
+        check(_lib.lib().vkn_stq_reset(ctypes.byref(cfg), _ptr(state), state.numel(), _stream()))
+    return state
+
+
+def stq_update(cfg, state, is_thing, gt_sem, gt_ins, pred_sem, pred_ins):
+    """Count B frames of one sequence into `state` (vkn_stq_update_i32, one launch, no synchronisation).  The four maps: int32 CUDA
+    tensors [H,W] or [B,H,W] of one shape; is_thing uint8 [n]."""
+    maps = [_req_plain(m, name, torch.int32) for m, name in zip((gt_sem, gt_ins, pred_sem, pred_ins), ('gt_sem', 'gt_ins', 'pred_sem', 'pred_ins'))]
+    shape = tuple(maps[0].shape)
+    if len(shape) not in (2, 3) or any(tuple(m.shape) != shape or m.device != state.device for m in maps):
+        raise ValueError(f'stq_update: four int32 maps [H,W] or [B,H,W] of one shape on the state\'s device, got {[tuple(m.shape) for m in maps]}')
+    B = shape[0] if len(shape) == 3 else 1
+    HW = shape[-2] * shape[-1]
+    thing = _req_plain(is_thing, 'is_thing', torch.uint8)
+    if thing.numel() < cfg.num_classes or thing.device != state.device:
+        raise ValueError(f'stq_update: is_thing must hold at least num_classes = {cfg.num_classes} bytes on the state\'s device')
+    with torch.cuda.device(state.device):
+        check(_lib.lib().vkn_stq_update_i32(ctypes.byref(cfg), _ptr(state), state.numel(), _ptr(thing), *[_ptr(m) for m in maps], int(B), int(HW),
+                                            _stream()))
