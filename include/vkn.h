@@ -832,8 +832,16 @@ int vkn_qd_tracker_match_f32(const VknTrackerCfg* cfg, void* state, size_t state
 /* ---- localization FPN of the kernel-initialisation head ("RPN"): `SemanticFPNWrapper` (knet/det/semantic_fpn_wrapper.py:33-237)
  *      + the head's `loc_convs` / `seg_convs` (knet/det/kernel_head.py:150-159, 207-230).  Replaces `self.localization_fpn(img)`
  *      and the loc / seg conv loops of `_decode_init_proposals` (:207-230): the whole upstream of vkn_kernel_init_f32.
- *      Convs are implicit GEMMs on MFMA with the two-term f16 split (2^-22 relative operands, fp32 accumulation); GroupNorm (eps
- *      1e-5, biased variance) and ReLU are applied by each conv's CONSUMER from fixed-order fp64-merged statistics (deterministic).
+ *      Convs are implicit GEMMs on MFMA with the two-term f16 split (fp32 accumulation); GroupNorm (eps 1e-5, biased variance) and
+ *      ReLU are applied by each conv's CONSUMER from fixed-order fp64-merged statistics (deterministic).
+ *      Operand resolution (holds for vkn_conv_gn_f32 and vkn_localization_fpn_f32 alike): 2^-22 relative wherever the low half of
+ *      the split is a normal f16.  Activations are staged UNSCALED, so a staged value 0 < |v| < 2^-3 has a subnormal low half and
+ *      an ABSOLUTE resolution of 2^-24 (6e-8), as the operands of vkn_mask_gather_real_f32; a weight is split after the matrix's
+ *      power-of-two pre-scale (max |w| scale in [2^14, 2^15)), so a weight with 0 < |w| scale < 2^-3 — below about 2^-17 of the
+ *      matrix's largest |w| — has the absolute resolution 2^-24 / scale.  Per output element that is
+ *        |out - exact| <= r sum |w v| + 2^-24 sum (|w| [0 < |v| < 2^-3] + |v| [0 < |w| scale < 2^-3] / scale),  r about 2^-22,
+ *      measured element by element (tests/test_gpu_fpn_conv_pins.py, profiles/fpn_conv_margins.json): outputs exceed the relative
+ *      part only where such an operand enters.  Feature maps far below unit scale should be scaled by a power of two first.
  *      Activations must stay inside the f16-split envelope (|v| < 65504, finite): otherwise VKN_STATUS_RANGE is ORed into the
  *      status word (the first four bytes of `ws`, vkn_workspace_status) and the outputs are garbage.
  *

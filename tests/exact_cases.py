@@ -362,7 +362,8 @@ def dw_batch_shapes(nitems):
     return [pool[i % len(pool)] for i in range(nitems)]
 
 
-# ---- FPN conv (the raw conv output of conv_gn; its statistics stay with the float rule of test_gpu_semantic_fpn.py)
+# ---- FPN conv (the raw conv output of conv_gn; its statistics are not linear: test_gpu_semantic_fpn.py judges them per tensor,
+#      test_gpu_fpn_conv_pins.py per group)
 CONV_SIZES = ((1, 1), (2, 3), (3, 5), (12, 39), (47, 155), (48, 156))
 
 
@@ -381,18 +382,215 @@ def conv_shapes():
     return out
 
 
-def conv_case(B, C, H, W, ks, stride, mode, seed):
-    """(x [B, C, H, W], pos [C, H, W] | None, w [C, C, ks, ks], out float64): conv2d(x + pos, w, stride, padding = ks // 2)"""
+def conv_case(B, C, H, W, ks, stride, mode, seed, Cout=None):
+    """(x [B, C, H, W], pos [C, H, W] | None, w [Cout, C, ks, ks], out float64): conv2d(x + pos, w, stride, padding = ks // 2);
+    Cout = C unless given"""
     g = gen(seed)
+    Cout = C if Cout is None else Cout
     x = ints((B, C, H, W), -4, 4, g)
     pos = ints((C, H, W), -4, 4, g) if mode == 'pos' else None
-    w = ints((C, C, ks, ks), -2, 2, g)
+    w = ints((Cout, C, ks, ks), -2, 2, g)
     xin = x.double() + (pos.double() if pos is not None else 0.0)
     out = F.conv2d(xin, w.double(), stride=stride, padding=ks // 2)
-    name = f'conv B{B} C{C} {H}x{W} k{ks} s{stride} {mode}'
+    name = f'conv B{B} C{C}->{Cout} {H}x{W} k{ks} s{stride} {mode}'
     premise(name, F.conv2d(xin.abs(), w.double().abs(), stride=stride, padding=ks // 2))
     non_vacuous(name, out)
     return x, pos, w, out
+
+
+# ---- FPN conv, per element (tests/test_gpu_fpn_conv_pins.py): the on-load transforms, Cin != Cout, single-pixel probes.
+# The engine works on 64-pixel runs of an output row, two 32-column MFMA blocks each; a wave owns two 32-row blocks of Cout, a grid
+# slice 256 rows.  Output widths around those edges, and the (Cin, Cout) pairs that leave a wave with ONE 32-row block (Cout = 32, 96,
+# 160, 288), fill both 256-row grid slices (Cout = 512) or run sixteen 32-channel chunks (Cin = 512):
+FPN_WO = (1, 31, 32, 33, 63, 64, 65, 128, 129)
+FPN_H = (1, 2, 3, 5)
+FPN_CC = ((32, 32), (64, 96), (96, 160), (32, 288), (512, 32), (256, 512))
+FPN_KS = ((3, 1), (3, 2), (1, 1))                 # (ksize, stride): a strided 1x1 conv is outside the envelope
+
+FpnCase = collections.namedtuple('FpnCase', 'B Cin Cout H W ks stride mode in_groups low seed')   # H x W: the SOURCE map (x)
+
+
+def fpn_id(c):
+    return f'{c.mode}{"_low" if c.low else ""}_B{c.B}_{c.Cin}to{c.Cout}_{c.H}x{c.W}_k{c.ks}s{c.stride}_g{c.in_groups}'
+
+
+def fpn_out_hw(c):
+    """(Hin, Win, Ho, Wo): the conv input ('up': 2H x 2W) and the output map (3x3 pad 1 and 1x1 pad 0: ceil(n / stride))"""
+    Hin, Win = (2 * c.H, 2 * c.W) if c.mode == 'up' else (c.H, c.W)
+    return Hin, Win, (Hin - 1) // c.stride + 1, (Win - 1) // c.stride + 1
+
+
+def _fpn_src_w(mode, Wo, stride):
+    """the source width that gives output width Wo (None: impossible — 'up' at stride 1 has Wo = 2 W), and the odd / even variant"""
+    if mode == 'up':
+        return Wo if stride == 2 else (Wo // 2 if Wo % 2 == 0 else None)
+    return Wo if stride == 1 else 2 * Wo - (Wo % 2)          # stride 2: Win = 2 Wo - 1 (odd) for odd Wo, 2 Wo (even) for even Wo
+
+
+def fpn_norm_shapes(mode):
+    """mode 'norm' / 'up': every (ksize, stride) at every output width of FPN_WO that the mode can produce.  The other axes rotate with
+    the WIDTH index, shifted per kernel variant, so that no axis is locked to a variant: along the widths every (ksize, stride) meets
+    every (Cin, Cout) pair, every in_groups form and every B (fpn_covers is the promise, test_exact_premise.py asserts it); then the
+    named edge cases."""
+    out, i = [], 0
+    for wi, Wo in enumerate(FPN_WO):
+        for ki, (ks, stride) in enumerate(FPN_KS):
+            W = _fpn_src_w(mode, Wo, stride)
+            if W is None:
+                continue
+            Cin, Cout = FPN_CC[(wi + 2 * ki) % len(FPN_CC)]
+            heavy = Cin * Cout >= 512 * 256 or Wo > 65
+            H = (1, 2)[(wi + ki) % 2] if heavy and mode == 'up' else FPN_H[(wi + ki) % 4]
+            B = 1 if heavy else (1, 2, 3)[(wi + 2 * ki) % 3]
+            out.append(FpnCase(B, Cin, Cout, H, W, ks, stride, mode, (1, 8, Cin)[(wi + ki) % 3], False, 3000 + 100 * (mode == 'up') + i))
+            i += 1
+    seed = 3300 + 100 * (mode == 'up')
+    if mode == 'up':      # both clamps are zero at Hs = 1 / Ws = 1; a source of one pixel
+        extra = [(2, 64, 96, 1, 33, 3, 1, 8), (2, 32, 32, 5, 1, 3, 1, 32), (1, 96, 160, 1, 1, 3, 2, 1), (3, 32, 288, 3, 1, 1, 1, 8),
+                 (1, 512, 32, 7, 65, 3, 2, 8), (1, 256, 512, 5, 33, 3, 1, 256)]
+    else:                 # stride 2 on odd and on even Hin / Win
+        extra = [(2, 64, 96, 3, 5, 3, 1, 8), (1, 32, 32, 5, 129, 3, 2, 32), (3, 96, 160, 2, 130, 3, 2, 1), (1, 32, 288, 4, 66, 3, 2, 8),
+                 (1, 512, 512, 2, 64, 1, 1, 512)]
+    out += [FpnCase(B, Ci, Co, H, W, ks, st, mode, G, False, seed + j) for j, (B, Ci, Co, H, W, ks, st, G) in enumerate(extra)]
+    return out
+
+
+def fpn_low_shapes():
+    """the cases whose staged activations carry bits in the LOW half of the f16 split (share >= FPN_LOW_SHARE, asserted per case; one
+    mean per channel where fewer groups leave the share below it)"""
+    rows = [('up', 2, 64, 96, 3, 5, 3, 1, 8), ('up', 1, 32, 160, 4, 66, 3, 2, 32), ('up', 1, 96, 32, 3, 32, 1, 1, 96),
+            ('up', 1, 32, 288, 2, 65, 3, 2, 32), ('up', 3, 64, 96, 5, 3, 3, 1, 64),
+            ('norm', 2, 32, 96, 3, 65, 3, 1, 8), ('norm', 1, 32, 160, 5, 129, 3, 2, 32), ('norm', 3, 32, 32, 2, 64, 1, 1, 1),
+            ('norm', 1, 32, 288, 1, 33, 3, 1, 8), ('norm', 1, 32, 512, 3, 63, 3, 2, 1)]
+    return [FpnCase(B, Ci, Co, H, W, ks, st, mode, G, True, 3500 + j) for j, (mode, B, Ci, Co, H, W, ks, st, G) in enumerate(rows)]
+
+
+FPN_LOW_SHARE = 0.2
+
+
+def fpn_covers(cases):
+    """what a list of FpnCase covers, as data"""
+    hw = [fpn_out_hw(c) for c in cases]
+    return dict(Wo={o[3] for o in hw}, H={c.H for c in cases}, B={c.B for c in cases}, CC={(c.Cin, c.Cout) for c in cases},
+                KS={(c.ks, c.stride) for c in cases}, groups={'Cin' if c.in_groups == c.Cin else c.in_groups for c in cases},
+                WoKS={(o[3], c.ks, c.stride) for c, o in zip(cases, hw)},
+                KS_CC={(c.ks, c.stride, c.Cin, c.Cout) for c in cases},
+                KS_groups={(c.ks, c.stride, 'Cin' if c.in_groups == c.Cin else c.in_groups) for c in cases},
+                KS_B={(c.ks, c.stride, c.B) for c in cases},
+                s2_parity={(o[0] % 2, o[1] % 2) for c, o in zip(cases, hw) if c.stride == 2},
+                one_row=any(c.H == 1 for c in cases), one_col=any(c.W == 1 for c in cases))
+
+
+def fpn_chain(x, stats, gamma, beta, up):
+    """what the conv's LOAD does, in x's dtype, as plain torch: GroupNorm from the given (mean, rstd) [B, G, 2] + affine + ReLU, then
+    (up) F.interpolate(scale_factor=2, bilinear, align_corners=False).  The operation order is the kernel's: ((v - mean) rstd) gamma + beta."""
+    B, C = x.shape[:2]
+    cpg = C // stats.shape[1]
+    mean = stats[..., 0].repeat_interleave(cpg, 1)[..., None, None].to(x.dtype)
+    rstd = stats[..., 1].repeat_interleave(cpg, 1)[..., None, None].to(x.dtype)
+    v = ((x - mean) * rstd * gamma.to(x.dtype)[None, :, None, None] + beta.to(x.dtype)[None, :, None, None]).clamp_min(0)
+    return F.interpolate(v, scale_factor=2, mode='bilinear', align_corners=False) if up else v
+
+
+def split_f16(v):
+    """the two-term f16 split of the staged activations, restated: hi = f16(v), lo = f16(v - hi), both round-to-nearest-even"""
+    v = v.float()
+    hi = v.half()
+    return hi, (v - hi.float()).half()
+
+
+def _pow2_unit(t):
+    """the largest power of two (<= 1) of which every element of the float64 tensor is a multiple"""
+    u = 1.0
+    while not bool((t / u == (t / u).round()).all()):
+        u /= 2
+        if u < 2.0 ** -30:
+            raise PremiseError('the operands are not dyadic')
+    return u
+
+
+def fpn_case(c):
+    """One 'norm' / 'up' case of dyadic operands -> dict(x, stats [B, G, 2], gamma, beta, w, xin (float64 conv input), out (float64),
+    unit, clip, low_share).
+      x integers in [-4, 4], mean k/4 in [-1, 1], rstd in {1/2, 1, 2}, gamma in {1/2, 1, 3/2}, beta k/4 in [-1, 1], w integers in [-2, 2]
+      low: x integers in [-32, 32], rstd = gamma = 1, mean k/64 ('up') or k/1024 ('norm') in [-1, 1], beta k/4 in [0, 2]
+    Every step is then exact in fp32 in any order and under any contraction.  Asserted here, from the operands: every staged value v
+    splits exactly (hi + lo == v), max sum (|hi| + |lo|) |w| < 2^24 units of the finest bit (low cases: < 2^23), non-zero outputs, a ReLU clip share in [0.05, 0.95],
+    and for low cases a share of staged values with lo != 0 of at least FPN_LOW_SHARE."""
+    g = gen(c.seed)
+    name = 'fpn ' + fpn_id(c)
+    G = c.in_groups
+    if c.low:
+        x = ints((c.B, c.Cin, c.H, c.W), -32, 32, g)
+        den = 64 if c.mode == 'up' else 1024
+        mean = ints((c.B, G), -den, den, g, den)
+        rstd = torch.ones(c.B, G)
+        gamma = torch.ones(c.Cin)
+        beta = ints((c.Cin,), 0, 8, g, 4)
+    else:
+        x = ints((c.B, c.Cin, c.H, c.W), -4, 4, g)
+        mean = ints((c.B, G), -4, 4, g, 4)
+        rstd = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (c.B, G), generator=g)]
+        gamma = torch.tensor([0.5, 1.0, 1.5])[torch.randint(0, 3, (c.Cin,), generator=g)]
+        beta = ints((c.Cin,), -4, 4, g, 4)
+    w = ints((c.Cout, c.Cin, c.ks, c.ks), -2, 2, g)
+    stats = torch.stack([mean, rstd], -1).contiguous()
+    up = c.mode == 'up'
+    pre = fpn_chain(x.double(), stats.double(), gamma.double(), beta.double(), False)
+    xin = fpn_chain(x.double(), stats.double(), gamma.double(), beta.double(), up)
+    out = F.conv2d(xin, w.double(), stride=c.stride, padding=c.ks // 2)
+    unit = _pow2_unit(xin)
+    hi, lo = split_f16(xin)
+    halves = hi.double().abs() + lo.double().abs()          # the accumulator sees hi w and lo w as separate terms
+    premise(name, F.conv2d(halves, w.double().abs(), stride=c.stride, padding=c.ks // 2) / unit, limit=TWO24 / 2 if c.low else TWO24)
+    non_vacuous(name, out)
+    if not torch.equal(hi.double() + lo.double(), xin):
+        raise PremiseError(name + ': a staged value does not split exactly into f16 hi + lo')
+    clip = float((pre == 0).double().mean())
+    if not 0.05 <= clip <= 0.95:
+        raise PremiseError(f'{name}: ReLU clip share {clip:.3f} outside [0.05, 0.95]')
+    low_share = float((lo != 0).double().mean())
+    if c.low and low_share < FPN_LOW_SHARE:
+        raise PremiseError(f'{name}: only {low_share:.3f} of the staged values have a non-zero low half (< {FPN_LOW_SHARE})')
+    return dict(x=x, stats=stats, gamma=gamma, beta=beta, w=w, xin=xin, out=out, unit=unit, clip=clip, low_share=low_share)
+
+
+# dense raw / pos cases (conv_case) at Cin != Cout: (B, Cin, Cout, H, W, ks, stride, mode)
+CONV_UNEQ = [(2, 64, 96, 3, 65, 3, 1, 'raw'), (1, 96, 160, 5, 129, 3, 2, 'pos'), (1, 256, 512, 2, 64, 3, 1, 'pos'), (1, 32, 288, 3, 33, 1, 1, 'raw'),
+             (1, 512, 32, 2, 31, 3, 2, 'raw'), (3, 32, 96, 1, 1, 3, 1, 'pos'), (1, 64, 160, 3, 130, 3, 2, 'raw'), (1, 512, 512, 2, 64, 1, 1, 'pos')]
+
+# single-pixel probes, modes raw / pos, Cin != Cout: the output is the weight stencil itself, a shifted or dropped tap names itself
+FPN_PROBE = [(2, 64, 96, 3, 65, 3, 1), (1, 96, 160, 5, 129, 3, 2), (1, 256, 512, 2, 128, 3, 1), (3, 32, 288, 3, 130, 3, 2), (1, 512, 32, 1, 64, 1, 1),
+             (2, 32, 512, 5, 66, 1, 1), (1, 64, 96, 1, 1, 3, 1), (1, 32, 160, 2, 257, 3, 2)]     # (B, Cin, Cout, H, W, ks, stride)
+
+
+def probe_pixels(H, W, stride):
+    """input pixels (y, x) under the image corners and under the first and the last output column of every 64-pixel run"""
+    Wo = (W - 1) // stride + 1
+    cols = {0, W - 1} | {min(ox * stride, W - 1) for t in range((Wo + 63) // 64) for ox in (64 * t, min(64 * t + 63, Wo - 1))}
+    return sorted({(y, x) for y in {0, H - 1, H // 2} for x in cols})
+
+
+def conv_probe_case(B, Cin, Cout, H, W, ks, stride, mode, seed):
+    """(x, pos | None, w [Cout, Cin, ks, ks] integers in [-2, 2] without zeros, out float64, n_probes).  Probe i sits in frame i % B on
+    input channel (5 i + 3) % Cin with value 1 + i % 3; mode 'pos': every second probe sits in `pos` instead (shared by the frames)."""
+    g = gen(seed)
+    x = torch.zeros(B, Cin, H, W)
+    pos = torch.zeros(Cin, H, W) if mode == 'pos' else None
+    w = ints((Cout, Cin, ks, ks), 1, 2, g) * (ints((Cout, Cin, ks, ks), 0, 1, g) * 2 - 1)
+    px = probe_pixels(H, W, stride)
+    for i, (y, xx) in enumerate(px):
+        ci, v = (5 * i + 3) % Cin, float(1 + i % 3)
+        if mode == 'pos' and i % 2:
+            pos[ci, y, xx] += v
+        else:
+            x[i % B, ci, y, xx] += v
+    xin = x.double() + (pos.double() if pos is not None else 0.0)
+    out = F.conv2d(xin, w.double(), stride=stride, padding=ks // 2)
+    name = f'conv probes B{B} {Cin}->{Cout} {H}x{W} k{ks} s{stride} {mode}'
+    premise(name, F.conv2d(xin.abs(), w.double().abs(), stride=stride, padding=ks // 2))
+    non_vacuous(name, out, *[out[b] for b in range(min(B, len(px)))])
+    return x, pos, w, out, len(px)
 
 
 # ---- autograd of gather / decode: the power-of-two scaling inside the backward must cancel exactly

@@ -1,4 +1,4 @@
-"""CPU: the premise of tests/test_gpu_exact.py, proved without a GPU.
+"""CPU: the premise of tests/test_gpu_exact.py and of the bit-for-bit part of tests/test_gpu_fpn_conv_pins.py, proved without a GPU.
 
 For every case of the sweep the case builders of exact_cases.py assert the PREMISE (max sum |terms| < 2^24 from the actual operands;
 fp16 outputs fit 11 bits) and NON-VACUITY (non-zero outputs, ON share in [0.05, 0.95], special rows as named).  Here, in addition,
@@ -149,3 +149,67 @@ def test_autograd_and_init_cases_hold():
             assert _same(F.conv2d(sem, sw[:, :, None, None], sb), ref['seg_preds']), sh
             obj = torch.einsum('bnhw,bchw->bnc', (mp.sigmoid() > 0.5).float(), sem + loc)
             assert _same(iw[None] + obj, ref['prop'][:, :iw.shape[0]]), sh
+
+
+# ---- the FPN conv per element (tests/test_gpu_fpn_conv_pins.py): on-load transforms, low halves, Cin != Cout, probes
+def test_fpn_shapes_cover_what_they_promise():
+    for mode in ('norm', 'up'):
+        c = ec.fpn_covers(ec.fpn_norm_shapes(mode))
+        assert c['Wo'] >= set(ec.FPN_WO) and c['H'] >= set(ec.FPN_H) and c['B'] == {1, 2, 3} and c['CC'] >= set(ec.FPN_CC), mode
+        assert c['KS'] == set(ec.FPN_KS) and c['groups'] == {1, 8, 'Cin'}, mode
+        for (ks, st) in (ec.FPN_KS if mode == 'norm' else ((3, 2),)):       # no axis is locked to a kernel variant ('up': the variant with all nine widths)
+            assert {(ci, co) for (k, s_, ci, co) in c['KS_CC'] if (k, s_) == (ks, st)} >= set(ec.FPN_CC), (mode, ks, st)
+            assert {g for (k, s_, g) in c['KS_groups'] if (k, s_) == (ks, st)} == {1, 8, 'Cin'}, (mode, ks, st)
+            assert {b for (k, s_, b) in c['KS_B'] if (k, s_) == (ks, st)} == {1, 2, 3}, (mode, ks, st)
+        for Wo in ec.FPN_WO:                                # every (ksize, stride) at every width the mode can produce
+            for (ks, st) in ec.FPN_KS:
+                possible = mode == 'norm' or st == 2 or Wo % 2 == 0          # 'up' at stride 1: Wo = 2 W
+                assert ((Wo, ks, st) in c['WoKS']) == possible, (mode, Wo, ks, st)
+        if mode == 'up':
+            assert c['one_row'] and c['one_col']            # Hs = 1, Ws = 1: both clamps of the bilinear taps are zero
+        else:
+            assert c['s2_parity'] == {(0, 0), (0, 1), (1, 0), (1, 1)}        # stride 2 on odd and even Hin / Win
+    low = ec.fpn_low_shapes()
+    assert {c.mode for c in low} == {'norm', 'up'} and all(c.Cin == 32 for c in low if c.mode == 'norm')
+    assert {c.Cout for c in low} >= {32, 96, 160, 288, 512} and {(c.ks, c.stride) for c in low} == set(ec.FPN_KS)
+    assert {co for (_, _, co, *_) in ec.CONV_UNEQ} >= {96, 160, 512} and all(ci != co or ci == 512 for (_, ci, co, *_) in ec.CONV_UNEQ)
+    assert {co for (_, _, co, *_) in ec.FPN_PROBE} >= {96, 160, 512} and all(ci != co for (_, ci, co, *_) in ec.FPN_PROBE)
+
+
+def test_a_fpn_case_outside_its_premise_fails_as_a_test_bug():
+    with pytest.raises(ec.PremiseError):                    # the low-half recipe at Cin = 512: sums of about 2^26 units of 2^-10
+        ec.fpn_case(ec.FpnCase(1, 512, 32, 3, 5, 3, 1, 'up', 512, True, 3599))
+    hi, lo = ec.split_f16(torch.tensor([1.0 + 2.0 ** -12, 3.0]))
+    assert lo.tolist() == [2.0 ** -12, 0.0] and hi.tolist() == [1.0, 3.0]
+
+
+@pytest.mark.parametrize('which', ['norm', 'up', 'low'])
+def test_fpn_load_chain_fp32_equals_float64_reference(which):
+    """torch's CPU fp32 chain (normalise, ReLU, bilinear x2) and its fp32 conv2d equal the float64 reference bit for bit on every case;
+    `fpn_case` itself asserts premise, exact split, non-vacuity, clip share and (low) the low-half share"""
+    cases = ec.fpn_low_shapes() if which == 'low' else ec.fpn_norm_shapes(which)
+    lows = []
+    for c in cases:
+        d = ec.fpn_case(c)
+        x32 = ec.fpn_chain(d['x'], d['stats'], d['gamma'], d['beta'], c.mode == 'up')
+        assert _same(x32, d['xin']), ('chain', c)
+        assert _same(F.conv2d(x32, d['w'], stride=c.stride, padding=c.ks // 2), d['out']), ('conv', c)
+        assert d['out'].shape[2:] == ec.fpn_out_hw(c)[2:], c
+        lows.append(d['low_share'])
+    if which == 'low':
+        assert min(lows) >= ec.FPN_LOW_SHARE
+    else:
+        assert max(lows) == 0.0                             # (the plain dyadic cases leave every low half zero: that is why `low` exists)
+
+
+def test_conv_unequal_channels_and_probes_fp32_equal_integer_reference():
+    for i, (B, Ci, Co, H, W, ks, stride, mode) in enumerate(ec.CONV_UNEQ):
+        x, pos, w, out = ec.conv_case(B, Ci, H, W, ks, stride, mode, 3600 + i, Cout=Co)
+        assert _same(F.conv2d(x + pos if pos is not None else x, w, stride=stride, padding=ks // 2), out), (B, Ci, Co, H, W, ks, stride, mode)
+    for i, (B, Ci, Co, H, W, ks, stride) in enumerate(ec.FPN_PROBE):
+        for mode in ('raw', 'pos'):
+            x, pos, w, out, n = ec.conv_probe_case(B, Ci, Co, H, W, ks, stride, mode, 3700 + i)
+            assert _same(F.conv2d(x + pos if pos is not None else x, w, stride=stride, padding=ks // 2), out), (B, Ci, Co, H, W, ks, stride, mode)
+            assert n >= 1 and int((x != 0).sum()) + (int((pos != 0).sum()) if pos is not None else 0) == n      # one pixel per probe
+    assert (0, 63) in ec.probe_pixels(3, 65, 1) and (0, 64) in ec.probe_pixels(3, 65, 1) and (2, 0) in ec.probe_pixels(3, 65, 1)
+    assert (4, 126) in ec.probe_pixels(5, 129, 2) and (4, 128) in ec.probe_pixels(5, 129, 2)                   # output columns 63 and 64

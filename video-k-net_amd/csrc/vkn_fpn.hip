@@ -3,7 +3,9 @@
 // (knet/det/kernel_head.py:150-159, 207-230), everything between the backbone's P2..P5 and `vkn_kernel_init_f32`.
 //
 // One engine, k_fpn_conv: an implicit GEMM out[co][px] = sum_{tap, ci} W[co][ci][tap] * in[ci][px + shift(tap)] on MFMA
-// (v_mfma_f32_32x32x16_f16, the two-term f16 split of vkn_common.h: hi*hi + hi*lo + lo*hi, fp32 accumulation, 2^-22 relative).
+// (v_mfma_f32_32x32x16_f16, the two-term f16 split of vkn_common.h: hi*hi + hi*lo + lo*hi, fp32 accumulation; 2^-22 relative where the
+// low half is a normal f16, absolute 2^-24 for staged activations below 2^-3 and for weights below 2^-3 after the pre-scale: the
+// resolution paragraph of include/vkn.h at the localization FPN).
 //   * workgroup = 4 waves = 256 output channels x one 64-pixel run of an output row; wave w owns channels 64w .. 64w+63
 //     (two 32-row MFMA blocks) x the 64 pixels (two 32-column blocks);
 //   * B operand (activations): per 32-channel chunk the input patch under the run (3 rows x (63 s + 3) columns for a 3x3 conv of
