@@ -21,6 +21,7 @@ from .track_train_tail import TrackTrainTail  # noqa: F401
 from .gt_prep import GtPrep  # noqa: F401
 from .seg_tail import SegLossTail  # noqa: F401
 from .stq_meter import STQMeter  # noqa: F401
+from .vpq_meter import VPQMeter  # noqa: F401
 from .registry import HEADS, TRANSFORMER_LAYER, build_head, build_transformer_layer  # noqa: F401
 from . import autograd, losses  # noqa: F401
 from .mask_pseudo_sampler import MaskPseudoSampler  # noqa: F401

@@ -1533,3 +1533,51 @@ def stq_update(cfg, state, is_thing, gt_sem, gt_ins, pred_sem, pred_ins):
     with torch.cuda.device(state.device):
         check(_lib.lib().vkn_stq_update_i32(ctypes.byref(cfg), _ptr(state), state.numel(), _ptr(thing), *[_ptr(m) for m in maps], int(B), int(HW),
                                             _stream()))
+
+
+# ---- the VPQ meter (include/vkn_vpq.h): one caller-owned state per sequence
+def vpq_cfg(num_cat, ks=(1,), ign_id=255, label_bit_shift=16, offset=2 ** 30, cap_gt=512, cap_pred=512, cap_pair=2048, cap_log=131072):
+    """The `VknVpqCfg` of a meter; raises VknError (VKN_E_SHAPE) outside the envelope of include/vkn_vpq.h."""
+    ks = tuple(int(k) for k in ks)
+    if not 1 <= len(ks) <= _lib.VPQ['VKN_VPQ_MAX_KS']:
+        raise _lib.VknError(-2, f'vpq_cfg: 1 to {_lib.VPQ["VKN_VPQ_MAX_KS"]} window lengths, got {ks}')
+    cfg = _lib.VknVpqCfg(int(offset), int(num_cat), int(ign_id), int(label_bit_shift), len(ks),
+                         (ctypes.c_int * _lib.VPQ['VKN_VPQ_MAX_KS'])(*ks), int(cap_gt), int(cap_pred), int(cap_pair), int(cap_log))
+    if not _lib.lib().vkn_vpq_state_bytes(ctypes.byref(cfg)):
+        raise _lib.VknError(-2, 'vpq_cfg: outside the envelope of include/vkn_vpq.h (num_cat 1..255 <= ign_id <= 255, shift 1..30, '
+                                'offset >= num_cat << shift, ((ign_id + 1) << shift) * offset < 2^62, ks ascending in 1..8, '
+                                'capacities powers of two in [16, 2^20])')
+    return cfg
+
+
+def vpq_layout(cfg):
+    """(state bytes, the four byte offsets: header, acc, log, private)"""
+    off = (ctypes.c_size_t * 4)()
+    check(_lib.lib().vkn_vpq_state_layout(ctypes.byref(cfg), off))
+    return int(_lib.lib().vkn_vpq_state_bytes(ctypes.byref(cfg))), [int(o) for o in off]
+
+
+def vpq_state(cfg, device):
+    """A freshly reset state of one sequence: uint8 [vkn_vpq_state_bytes] on `device`."""
+    state = torch.empty((vpq_layout(cfg)[0],), dtype=torch.uint8, device=device)
+    return vpq_reset(cfg, state)
+
+
+def vpq_reset(cfg, state):
+    """Empty the state (vkn_vpq_reset, one fill); returns it."""
+    with torch.cuda.device(state.device):
+        check(_lib.lib().vkn_vpq_reset(ctypes.byref(cfg), _ptr(state), state.numel(), _stream()))
+    return state
+
+
+def vpq_update(cfg, state, gt_sem, gt_ins, pred_sem, pred_ins):
+    """Count B consecutive frames of one sequence into `state` and close every window that ends in them (vkn_vpq_update_i32, three
+    launches per VKN_VPQ_GROUP frames, no synchronisation).  The four maps: int32 CUDA tensors [H,W] or [B,H,W] of one shape."""
+    maps = [_req_plain(m, name, torch.int32) for m, name in zip((gt_sem, gt_ins, pred_sem, pred_ins), ('gt_sem', 'gt_ins', 'pred_sem', 'pred_ins'))]
+    shape = tuple(maps[0].shape)
+    if len(shape) not in (2, 3) or any(tuple(m.shape) != shape or m.device != state.device for m in maps):
+        raise ValueError(f'vpq_update: four int32 maps [H,W] or [B,H,W] of one shape on the state\'s device, got {[tuple(m.shape) for m in maps]}')
+    B = shape[0] if len(shape) == 3 else 1
+    HW = shape[-2] * shape[-1]
+    with torch.cuda.device(state.device):
+        check(_lib.lib().vkn_vpq_update_i32(ctypes.byref(cfg), _ptr(state), state.numel(), *[_ptr(m) for m in maps], int(B), int(HW), _stream()))
