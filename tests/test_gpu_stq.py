@@ -101,6 +101,25 @@ def test_maps_that_start_off_the_16_byte_grid(vkn):
         _same_tables(meter.tables(0), ref.tables(0), f'skews {skews}')
 
 
+def test_one_map_alone_off_gt_sems_residue(vkn):
+    """gt_ins, pred_sem, pred_ins in turn on a residue of its own: that map is loaded by words, the other three by 16 bytes.  Two frames
+    of 375 pixels: the second one starts behind a peel"""
+    maps = [m.reshape(2, 3, 125) for m in stq_ref.seeded_maps(9, 6, 125, cell=4)]
+    ref = stq_ref.STQRef(**K)
+    ref.update_state(*maps)
+    for skews in ((0, 1, 0, 0), (0, 0, 2, 0), (0, 0, 0, 3)):
+        views = []
+        for m, k in zip(maps, skews):
+            v = torch.zeros((m.size + 4,), dtype=torch.int32, device=DEV)[k:k + m.size].view(m.shape)
+            v.copy_(torch.from_numpy(m))
+            assert v.data_ptr() % 16 == 4 * k
+            views.append(v)
+        meter = vkn.STQMeter(**K, device=DEV)
+        meter.update_state(*views)
+        _same_tables(meter.tables(0), ref.tables(0), f'skews {skews}')
+        assert meter.tables(0)['status'] == 0 and meter.tables(0)['frames'] == 2
+
+
 def test_lds_overflow_takes_the_global_path(vkn):
     p = stq_ref.LDS_OVERFLOW
     _against_ref(vkn, stq_ref.noisy_maps(p['seed'], p['H'], p['W']), 'LDS overflow')

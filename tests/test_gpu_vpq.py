@@ -108,6 +108,24 @@ def test_odd_frame_size_and_maps_off_the_16_byte_grid(vkn):
         vpq_ref.assert_same_tables(meter.tables(0), want, f'skews {skews}')
 
 
+def test_one_map_alone_off_gt_sems_residue(vkn):
+    """gt_ins, pred_sem, pred_ins in turn on a residue of its own: that map is loaded by words, the other three by 16 bytes.  Two frames
+    of 897 pixels: the second one starts behind a peel"""
+    maps = [np.ascontiguousarray(m[:2]) for m in _video('SMALL')[0]]
+    ref = vpq_ref.VPQRef(**K)
+    ref.update_state(*maps)
+    for skews in ((0, 1, 0, 0), (0, 0, 2, 0), (0, 0, 0, 3)):
+        views = []
+        for m, k in zip(maps, skews):
+            v = torch.zeros((m.size + 4,), dtype=torch.int32, device=DEV)[k:k + m.size].view(m.shape)
+            v.copy_(torch.from_numpy(m))
+            assert v.data_ptr() % 16 == 4 * k
+            views.append(v)
+        meter = vkn.VPQMeter(**K, device=DEV)
+        _feed(meter, views, [2])
+        vpq_ref.assert_same_tables(meter.tables(0), ref.tables(0), f'skews {skews}')
+
+
 def test_tail_and_peel_arms(vkn):
     span = vkn._lib.VPQ['VKN_VPQ_SPAN_PX']
     for HW in (1, 3, 5, span - 1, span, span + 1):

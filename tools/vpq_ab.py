@@ -1,6 +1,7 @@
 """A/B of one VPQ `update_state` with ks = (1, 2, 4, 6): the device meter (`VPQMeter`, csrc/vkn_vpq.hip: per VKN_VPQ_GROUP frames one clear,
 one count and one window launch, no host read) beside
-    stq      `STQMeter.update_state` on the same maps (csrc/vkn_stq.hip: the same 16 bytes per pixel, one launch);
+    stq      `STQMeter.update_state` on the same maps (csrc/vkn_stq.hip: the same 16 bytes per pixel through the same counting engine,
+             csrc/vkn_mapcount.h, one launch);
     copy     the device -> host copy of the four int32 maps alone, wall clock with a synchronisation;
     host     copy + the NumPy restatement tests/vpq_ref.py (one np.unique per table and frame, then dicts per window: already far less
              work than the scripts' three np.unique sorts per window and window length; the reference itself is not needed).

@@ -98,6 +98,18 @@ __device__ __forceinline__ float vkn_wave_max(float v) {
 #define VKN_STATUS_RANGE 1
 #endif
 
+// The entry points' pointer checks.  vkn_on_device: a pointer the kernels may dereference, device (or managed) memory; host pointers are
+// refused before anything is launched.
+static inline bool vkn_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+static inline bool vkn_on_device(const void* p) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
 // Raise a kernel's dynamic-LDS limit to the whole 160 KB ONCE per (process, device) instead of on every launch.
 static inline int vkn_allow_full_lds(const void* fn, unsigned long long* done_mask) {
     int dev = 0;

@@ -18,16 +18,6 @@ struct GtBatch { VknGtImage img[VKN_GT_MAX_IMAGES]; };
 struct GtTable { int label[VKN_GT_MAX_CLASSES]; };
 struct GtOffsets { int key[VKN_GT_MAX_IMAGES + 1], ref[VKN_GT_MAX_IMAGES + 1]; };
 
-inline bool gt_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-inline bool gt_on_device(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 // ------------------------------------------------------------------------------------------------------------ class presence
 __device__ __forceinline__ void gp_mark(unsigned* bits, int v, int& last) {
     if (v != last) {               // semantic maps are piecewise constant: most pixels repeat their left neighbour
@@ -306,15 +296,15 @@ int vkn_gt_classes(const VknGtImage* imgs, int B, int Hp, int Wp, int sem_i64, c
     if (Hp < 1 || Wp < 1 || (long long)Hp * Wp >= (1ll << 31) || Hp > GP_ROWS * 65535) return VKN_E_SHAPE;   // grid.x of the presence pass
     for (int b = 0; b < B; ++b)
         if (imgs[b].valid_h < 0 || imgs[b].valid_h > Hp || imgs[b].valid_w < 0 || imgs[b].valid_w > Wp) return VKN_E_SHAPE;
-    if (!gt_aligned(flags, 4) || !gt_aligned(n_sem, 4) || !gt_aligned(labels, 8) || !gt_aligned(status, 4)) return VKN_E_ALIGN;
+    if (!vkn_aligned(flags, 4) || !vkn_aligned(n_sem, 4) || !vkn_aligned(labels, 8) || !vkn_aligned(status, 4)) return VKN_E_ALIGN;
     for (int b = 0; b < B; ++b)
-        if (sem_i64 && !gt_aligned(imgs[b].sem, 8)) return VKN_E_ALIGN;
+        if (sem_i64 && !vkn_aligned(imgs[b].sem, 8)) return VKN_E_ALIGN;
     const void* ptrs[] = {flags, n_sem, classes, labels, status};
     for (const void* p : ptrs)
-        if (!gt_on_device(p)) return VKN_E_ARG;
+        if (!vkn_on_device(p)) return VKN_E_ARG;
     GtBatch batch = {};
     for (int b = 0; b < B; ++b) {
-        if (!gt_on_device(imgs[b].sem)) return VKN_E_ARG;
+        if (!vkn_on_device(imgs[b].sem)) return VKN_E_ARG;
         batch.img[b] = imgs[b];
     }
     GtTable tab;
@@ -355,14 +345,14 @@ int vkn_gt_bank_fill_f32(const VknGtImage* imgs, int B, int Hp, int Wp, int s, i
         units += im.G + (im.n_sem > 0 ? 1 : 0);
     }
     if (units > 65535) return VKN_E_SHAPE;
-    if (!gt_aligned(bank, 16)) return VKN_E_ALIGN;
+    if (!vkn_aligned(bank, 16)) return VKN_E_ALIGN;
     for (int b = 0; b < B; ++b)
-        if (sem_i64 && imgs[b].n_sem > 0 && !gt_aligned(imgs[b].sem, 8)) return VKN_E_ALIGN;
-    if (!gt_on_device(bank)) return VKN_E_ARG;
+        if (sem_i64 && imgs[b].n_sem > 0 && !vkn_aligned(imgs[b].sem, 8)) return VKN_E_ALIGN;
+    if (!vkn_on_device(bank)) return VKN_E_ARG;
     GtBatch batch = {};
     for (int b = 0; b < B; ++b) {
         const VknGtImage& im = imgs[b];
-        if ((im.G > 0 && !gt_on_device(im.masks)) || (im.n_sem > 0 && (!gt_on_device(im.sem) || !gt_on_device(im.classes)))) return VKN_E_ARG;
+        if ((im.G > 0 && !vkn_on_device(im.masks)) || (im.n_sem > 0 && (!vkn_on_device(im.sem) || !vkn_on_device(im.classes)))) return VKN_E_ARG;
         batch.img[b] = im;
     }
     if (units == 0) return VKN_OK;
@@ -392,9 +382,9 @@ int vkn_gt_match_indices(const int64_t* key_ids, const int* key_len, const int64
         off.ref[b + 1] = off.ref[b] + ref_len[b];
     }
     if ((off.key[B] > 0 && (!key_ids || !match)) || (off.ref[B] > 0 && !ref_ids)) return VKN_E_ARG;
-    if (!gt_aligned(key_ids, 8) || !gt_aligned(ref_ids, 8) || !gt_aligned(match, 8) || !gt_aligned(match_off, 8)) return VKN_E_ALIGN;
-    if (!gt_on_device(match_off) || (off.key[B] > 0 && (!gt_on_device(key_ids) || !gt_on_device(match))) ||
-        (off.ref[B] > 0 && !gt_on_device(ref_ids)))
+    if (!vkn_aligned(key_ids, 8) || !vkn_aligned(ref_ids, 8) || !vkn_aligned(match, 8) || !vkn_aligned(match_off, 8)) return VKN_E_ALIGN;
+    if (!vkn_on_device(match_off) || (off.key[B] > 0 && (!vkn_on_device(key_ids) || !vkn_on_device(match))) ||
+        (off.ref[B] > 0 && !vkn_on_device(ref_ids)))
         return VKN_E_ARG;
 
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -19,16 +19,6 @@ constexpr int ST_CHUNK = 256;                  // layers staged in LDS at a time
 
 struct SegBatch { VknSegImage img[VKN_SEG_MAX_IMAGES]; };
 
-inline bool seg_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-inline bool seg_on_device(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 // --------------------------------------------------------------------------------------------------------------------- targets
 // grid (ceil(W / ST_COLS), ceil(H / ST_ROWS), B).  The layers of the image — n_sem stuff masks, then the Np proposal rows — are staged
 // in LDS in chunks of ST_CHUNK as (plane, label); label -1: the row paints nothing.  A thread walks them from the LAST one down and
@@ -446,17 +436,17 @@ int vkn_seg_targets_u8(const VknSegImage* imgs, int B, int H, int W, int ncls, u
     if (ncls < 1 || ncls > VKN_SEG_MAX_CLASSES || H < 1 || W < 1 || (long long)H * W >= (1ll << 31) || H > ST_ROWS * 65535) return VKN_E_SHAPE;
     for (int b = 0; b < B; ++b)
         if (imgs[b].G > VKN_SEG_MAX_ROWS || imgs[b].Np > VKN_SEG_MAX_ROWS || imgs[b].n_sem > VKN_SEG_MAX_ROWS) return VKN_E_SHAPE;
-    if (!seg_aligned(dense_pos, 4) || !seg_aligned(status, 4)) return VKN_E_ALIGN;
+    if (!vkn_aligned(dense_pos, 4) || !vkn_aligned(status, 4)) return VKN_E_ALIGN;
     for (int b = 0; b < B; ++b)
-        if (!seg_aligned(imgs[b].masks, 4) || !seg_aligned(imgs[b].sem, 4) || !seg_aligned(imgs[b].labels, 8) ||
-            !seg_aligned(imgs[b].sem_cls, 8) || !seg_aligned(imgs[b].gt_inds, 8))
+        if (!vkn_aligned(imgs[b].masks, 4) || !vkn_aligned(imgs[b].sem, 4) || !vkn_aligned(imgs[b].labels, 8) ||
+            !vkn_aligned(imgs[b].sem_cls, 8) || !vkn_aligned(imgs[b].gt_inds, 8))
             return VKN_E_ALIGN;
-    if (!seg_on_device(tgt) || !seg_on_device(dense_pos) || !seg_on_device(status)) return VKN_E_ARG;
+    if (!vkn_on_device(tgt) || !vkn_on_device(dense_pos) || !vkn_on_device(status)) return VKN_E_ARG;
     SegBatch batch = {};
     for (int b = 0; b < B; ++b) {
         const VknSegImage& im = imgs[b];
-        if ((im.G > 0 && (!seg_on_device(im.masks) || !seg_on_device(im.labels))) ||
-            (im.sem && im.n_sem > 0 && (!seg_on_device(im.sem) || !seg_on_device(im.sem_cls))) || (im.Np > 0 && !seg_on_device(im.gt_inds)))
+        if ((im.G > 0 && (!vkn_on_device(im.masks) || !vkn_on_device(im.labels))) ||
+            (im.sem && im.n_sem > 0 && (!vkn_on_device(im.sem) || !vkn_on_device(im.sem_cls))) || (im.Np > 0 && !vkn_on_device(im.gt_inds)))
             return VKN_E_ARG;
         batch.img[b] = im;
     }
@@ -481,9 +471,9 @@ int vkn_seg_loss_fwd_f32(const float* low, const unsigned char* tgt, const int* 
     if (!low || !tgt || !loss || !state || (mode == VKN_SEG_LOSS_FOCAL && !dense_pos)) return VKN_E_ARG;
     const int rc = seg_check_shape(mode, B, ncls, h, w, S);
     if (rc != VKN_OK) return rc;
-    if (!seg_aligned(low, 4) || !seg_aligned(loss, 4) || !seg_aligned(dense_pos, 4) || !seg_aligned(state, 16)) return VKN_E_ALIGN;
-    if (!seg_on_device(low) || !seg_on_device(tgt) || !seg_on_device(loss) || !seg_on_device(state) ||
-        (mode == VKN_SEG_LOSS_FOCAL && !seg_on_device(dense_pos)))
+    if (!vkn_aligned(low, 4) || !vkn_aligned(loss, 4) || !vkn_aligned(dense_pos, 4) || !vkn_aligned(state, 16)) return VKN_E_ALIGN;
+    if (!vkn_on_device(low) || !vkn_on_device(tgt) || !vkn_on_device(loss) || !vkn_on_device(state) ||
+        (mode == VKN_SEG_LOSS_FOCAL && !vkn_on_device(dense_pos)))
         return VKN_E_ARG;
     const SegShape s = seg_shape(ncls, h, w);
     const int n = s.gx * s.gy * B;
@@ -506,8 +496,8 @@ int vkn_seg_loss_bwd_f32(const float* low, const unsigned char* tgt, const float
     if (!low || !tgt || !gout || !state || !grad_low) return VKN_E_ARG;
     const int rc = seg_check_shape(mode, B, ncls, h, w, S);
     if (rc != VKN_OK) return rc;
-    if (!seg_aligned(low, 4) || !seg_aligned(gout, 4) || !seg_aligned(grad_low, 4) || !seg_aligned(state, 16)) return VKN_E_ALIGN;
-    if (!seg_on_device(low) || !seg_on_device(tgt) || !seg_on_device(gout) || !seg_on_device(state) || !seg_on_device(grad_low))
+    if (!vkn_aligned(low, 4) || !vkn_aligned(gout, 4) || !vkn_aligned(grad_low, 4) || !vkn_aligned(state, 16)) return VKN_E_ALIGN;
+    if (!vkn_on_device(low) || !vkn_on_device(tgt) || !vkn_on_device(gout) || !vkn_on_device(state) || !vkn_on_device(grad_low))
         return VKN_E_ARG;
     const SegShape s = seg_shape(ncls, h, w);
     const int n = s.gx * s.gy * B;

@@ -27,15 +27,6 @@ constexpr int TL_EC = 32;                         // embedding columns staged pe
 constexpr float TL_EPS = 1e-12f;                  // F.normalize's clamp on the norm
 constexpr int TL_SMALL = 8 * TL_MAX * 4 + 2 * TL_MAX * 4 + 256 * 4 + 64 * 4;   // the small LDS arrays of k_tl_fwd, bytes
 
-inline bool tl_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool tl_on_device(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
 inline size_t tl_pad(size_t n) { return (n + 255) & ~(size_t)255; }
 // workspace: part fp32 [B][2] (per-image losses), then per image: hdr int32 [4] (Kk, Kr), krow, rrow int32 [N], nk, nr fp32 [N]
 // (raw norms), cd, cc, cos fp32 [N * N] (leading dimension Kr)
@@ -522,12 +513,12 @@ int vkn_track_loss_fwd_f32(const VknTrackLossCfg* cfg, const float* key_embeds, 
     if (rc != VKN_OK) return rc;
     const void* ptrs[] = {key_embeds, ref_embeds, key_gt, ref_gt, match, match_off, losses, stats};
     for (const void* p : ptrs)
-        if (!tl_aligned16(p)) return VKN_E_ALIGN;
+        if (!vkn_aligned(p, 16)) return VKN_E_ALIGN;
     if (reinterpret_cast<uintptr_t>(status) & 3) return VKN_E_ALIGN;
-    if (!ws || ws_bytes < tl_ws_bytes(B, N) || !tl_aligned16(ws)) return VKN_E_WORKSPACE;
+    if (!ws || ws_bytes < tl_ws_bytes(B, N) || !vkn_aligned(ws, 16)) return VKN_E_WORKSPACE;
     for (const void* p : ptrs)
-        if (!tl_on_device(p)) return VKN_E_ARG;
-    if (!tl_on_device(status) || !tl_on_device(ws) || (aux_kept && !tl_on_device(aux_kept))) return VKN_E_ARG;
+        if (!vkn_on_device(p)) return VKN_E_ARG;
+    if (!vkn_on_device(status) || !vkn_on_device(ws) || (aux_kept && !vkn_on_device(aux_kept))) return VKN_E_ARG;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     VKN_ALLOW_FULL_LDS(k_tl_fwd);
@@ -549,11 +540,11 @@ int vkn_track_loss_bwd_f32(const VknTrackLossCfg* cfg, const float* key_embeds, 
     if (rc != VKN_OK) return rc;
     const void* ptrs[] = {key_embeds, ref_embeds, gout, d_key, d_ref};
     for (const void* p : ptrs)
-        if (!tl_aligned16(p)) return VKN_E_ALIGN;
-    if (!ws || ws_bytes < tl_ws_bytes(B, N) || !tl_aligned16(ws)) return VKN_E_WORKSPACE;
+        if (!vkn_aligned(p, 16)) return VKN_E_ALIGN;
+    if (!ws || ws_bytes < tl_ws_bytes(B, N) || !vkn_aligned(ws, 16)) return VKN_E_WORKSPACE;
     for (const void* p : ptrs)
-        if (!tl_on_device(p)) return VKN_E_ARG;
-    if (!tl_on_device(ws)) return VKN_E_ARG;
+        if (!vkn_on_device(p)) return VKN_E_ARG;
+    if (!vkn_on_device(ws)) return VKN_E_ARG;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     VKN_ALLOW_FULL_LDS(k_tl_bwd);

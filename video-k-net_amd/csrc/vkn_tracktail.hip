@@ -21,18 +21,6 @@ constexpr int TT_MAX_K = VKN_TRACK_MAX_K;   // entries per frame (LDS tables)
 constexpr int TT_TW = 64, TT_TH = 16;       // map tile of one workgroup of the box pass: 256 threads x 4 pixels of one row
 constexpr int TT_EMPTY_MIN = 0x7fffffff;
 
-inline bool tt_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// A pointer the kernels may dereference: device (or managed) memory.  Host pointers are refused before anything is launched.
-inline bool tt_on_device(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 inline size_t tt_pad(size_t n) { return (n + 255) & ~(size_t)255; }
 // boxes workspace: slot_of [B][K + 1] (segment id -> compact slot or -1), box [B][K][4] (xmin, ymin, xmax, ymax)
 inline size_t tt_boxes_ws(int B, int K) { return tt_pad((size_t)B * (K + 1) * 4) + tt_pad((size_t)B * K * 16); }
@@ -325,11 +313,11 @@ int vkn_track_boxes_f32(const int* panoptic_seg, const int* info, const int* nse
     if (sem_logits && (unsigned long long)Cs * hs * ws_w * 4ull >= (1ull << 31)) return VKN_E_SHAPE;
     const void* ptrs[] = {panoptic_seg, info, nseg, det, labels, rows, segid, count, sem_logits, thing_mask};
     for (const void* p : ptrs)
-        if (p && !tt_aligned16(p)) return VKN_E_ALIGN;
-    if (!ws || ws_bytes < tt_boxes_ws(B, K) || !tt_aligned16(ws)) return VKN_E_WORKSPACE;
+        if (p && !vkn_aligned(p, 16)) return VKN_E_ALIGN;
+    if (!ws || ws_bytes < tt_boxes_ws(B, K) || !vkn_aligned(ws, 16)) return VKN_E_WORKSPACE;
     for (const void* p : ptrs)
-        if (p && !tt_on_device(p)) return VKN_E_ARG;
-    if (!tt_on_device(ws)) return VKN_E_ARG;
+        if (p && !vkn_on_device(p)) return VKN_E_ARG;
+    if (!vkn_on_device(ws)) return VKN_E_ARG;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     int* slot_of = static_cast<int*>(ws);
@@ -367,11 +355,11 @@ int vkn_track_maps_i32(const int* panoptic_seg, const int* segid, const int* cou
     if ((reinterpret_cast<uintptr_t>(n_ids) & 3) || (reinterpret_cast<uintptr_t>(sem_of_label) & 3)) return VKN_E_ALIGN;
     const void* ptrs[] = {panoptic_seg, segid, count, ids, info, track_map, semantic_map};
     for (const void* p : ptrs)
-        if (!tt_aligned16(p)) return VKN_E_ALIGN;
-    if (!ws || ws_bytes < tt_maps_ws(B, K) || !tt_aligned16(ws)) return VKN_E_WORKSPACE;
+        if (!vkn_aligned(p, 16)) return VKN_E_ALIGN;
+    if (!ws || ws_bytes < tt_maps_ws(B, K) || !vkn_aligned(ws, 16)) return VKN_E_WORKSPACE;
     for (const void* p : ptrs)
-        if (!tt_on_device(p)) return VKN_E_ARG;
-    if (!tt_on_device(n_ids) || !tt_on_device(sem_of_label) || !tt_on_device(ws)) return VKN_E_ARG;
+        if (!vkn_on_device(p)) return VKN_E_ARG;
+    if (!vkn_on_device(n_ids) || !vkn_on_device(sem_of_label) || !vkn_on_device(ws)) return VKN_E_ARG;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     int* lut = static_cast<int*>(ws);

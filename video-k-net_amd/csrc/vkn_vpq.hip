@@ -2,10 +2,10 @@
 // window length, from the four int32 maps of B consecutive frames.
 //
 // A window's areas are the sums of its frames' areas, so the pixels are read ONCE: k_vpq_count counts each frame into that frame's slot
-// of a ring of per-frame tables (gt areas, pred areas, pair areas) with the scheme of k_stq_update — spans of VKN_VPQ_SPAN_PX pixels, one
-// 16-byte load per map behind the span's peel, a running (key, count) per lane and kind, ONE table in LDS per workgroup, then per
-// occupied slot a 64-bit compare-and-swap on the key and a 64-bit add on the count at agent scope.  A workgroup stays inside one frame,
-// so the LDS key needs no frame tag.  k_vpq_window never touches a pixel: one workgroup per (frame f, window length k) sums the ring slots
+// of a ring of per-frame tables (gt areas, pred areas, pair areas) with the counting engine of vkn_mapcount.h, three kinds of count: spans
+// of VKN_VPQ_SPAN_PX pixels, ONE table in LDS per workgroup, then per occupied slot one insert into the frame's open-addressing tables at
+// agent scope.  A workgroup stays inside one frame, so the LDS key needs no frame tag.
+// k_vpq_window never touches a pixel: one workgroup per (frame f, window length k) sums the ring slots
 // of frames f - k + 1 .. f into window tables and runs the matching in three phases over those tables.  The window tables live in LDS
 // when they fit its 160 KiB less 4 KiB of counters (the default capacities take 52 KiB), else in the state's scratch.  Frames of a call share the launches in
 // groups of VKN_VPQ_GROUP: clear the group's ring slots, count, windows; the ring holds the max(ks) - 1 frames before a group and the
@@ -15,6 +15,7 @@
 // scratch every access is an agent-scope atomic (performed at L2, never served from the CU's L1) and the barrier comes with an agent fence.
 #include "../../include/vkn_vpq.h"
 #include "vkn_common.h"
+#include "vkn_mapcount.h"
 
 namespace {
 
@@ -22,13 +23,8 @@ constexpr int VPQ_THREADS = 256;
 constexpr int VPQ_WIN_THREADS = 1024;            // a window's workgroup: its work is chains of dependent table accesses, hidden by waves
 constexpr size_t VPQ_WIN_STATIC_LDS = 4096;        // the window kernel's own LDS
 constexpr size_t VPQ_LDS_BYTES = 160 * 1024 - VPQ_WIN_STATIC_LDS;      // window tables up to this size live in LDS
-constexpr int VPQ_LDS_PROBES = 32;                 // slots tried in LDS before a count goes to global memory directly
-constexpr unsigned long long VPQ_EMPTY = ~0ull;    // no tagged key is all ones: kind 3 does not exist
 constexpr long long VPQ_MATCHED = 1ll << 62;       // on a window table's count: the segment has a true positive (areas stay below 2^34)
 enum { K_PAIR = 0, K_GT = 1, K_PRED = 2 };
-static_assert((VKN_VPQ_LDS_SLOTS & (VKN_VPQ_LDS_SLOTS - 1)) == 0 && VKN_VPQ_SPAN_PX % (4 * VPQ_THREADS) == 0, "span / table geometry");
-constexpr int VPQ_CNT_BITS = 6;                    // a lane counts at most SPAN_PX / THREADS body pixels + 1 head or tail pixel
-static_assert(VKN_VPQ_SPAN_PX / VPQ_THREADS + 1 < (1 << VPQ_CNT_BITS), "a lane's run count must fit VPQ_CNT_BITS");
 static_assert(VKN_VPQ_GROUP <= VKN_VPQ_MAX_GRID, "a group's frames each get a workgroup");
 
 struct VpqLayout {
@@ -59,15 +55,6 @@ struct VpqArgs {
     int num_cat, ign, shift, nk, ks[VKN_VPQ_MAX_KS], cap_log, R;
 };
 
-inline bool vpq_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-inline bool vpq_on_device(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
 inline bool vpq_cap_ok(int cap) { return cap >= VKN_VPQ_MIN_CAP && cap <= VKN_VPQ_MAX_CAP && (cap & (cap - 1)) == 0; }
 
 inline int vpq_check_cfg(const VknVpqCfg* c) {
@@ -123,52 +110,48 @@ inline VpqTables vpq_tables(const VknVpqCfg* c) {
     return t;
 }
 
-// The keys are a few small fields far apart (class << 16 | id, and gt_id * offset + pred_id): one multiplication leaves the low bits of
-// either half poor in them (2400 such pair keys had 299 distinct homes among 8192 slots, probe chains of up to 42), so every bit is folded
-// down twice around two multiplications (the 64-bit finaliser of MurmurHash3: 2087 homes, chains of up to 11).
-__device__ __forceinline__ unsigned vpq_hash(unsigned long long k) {
-    k ^= k >> 33;
-    k *= 0xFF51AFD7ED558CCDull;
-    k ^= k >> 33;
-    k *= 0xC4CEB9FE1A85EC53ull;
-    k ^= k >> 33;
-    return (unsigned)k;
-}
+// a counting workgroup's state, and what mapcount needs to know of the meter
+struct VpqLds {
+    static constexpr int KINDS = 3, SLOTS = VKN_VPQ_LDS_SLOTS, THREADS = VPQ_THREADS, SPAN_PX = VKN_VPQ_SPAN_PX;
+    unsigned long long keys[SLOTS];
+    unsigned counts[SLOTS];
+    VpqArgs a;                        // the launch's arguments: the out-of-line helpers index its tables by kind
+    long long* slot;                  // the frame's ring slot
+    unsigned flags;
 
-// one (key, count) into a set of tables at `base`: the key slot by compare-and-swap, at most `cap` slots, then the count.  SC: the scope
-// of the atomics: agent for tables in global memory, workgroup for a window's tables in LDS.
+    // The keys are a few small fields far apart (class << 16 | id, and gt_id * offset + pred_id): one multiplication leaves the low bits
+    // of either half poor in them (2400 such pair keys had 299 distinct homes among 8192 slots, probe chains of up to 42), so every bit
+    // is folded down twice around two multiplications (the 64-bit finaliser of MurmurHash3: 2087 homes, chains of up to 11).
+    static __device__ __forceinline__ unsigned hash(unsigned long long k) {
+        k ^= k >> 33;
+        k *= 0xFF51AFD7ED558CCDull;
+        k ^= k >> 33;
+        k *= 0xC4CEB9FE1A85EC53ull;
+        k ^= k >> 33;
+        return (unsigned)k;
+    }
+    static __device__ __noinline__ void sink(const VpqLds& s, int kind, unsigned long long key, unsigned cnt);
+    static __device__ __forceinline__ void pixel(VpqLds& s, const VpqArgs& a, mapcount::Run (&run)[3], unsigned& flags, int gs, int gi, int ps, int pi);
+};
+
+// one (key, count) into a set of tables at `base`.  SC: the scope of the atomics: agent for tables in global memory, workgroup for a
+// window's tables in LDS.
 template <int SC>
 __device__ __forceinline__ void vpq_table_add_t(const VpqArgs& a, long long* base, int kind, unsigned long long key, unsigned long long cnt) {
-    long long* keys = base + a.t.keys[kind];
-    const unsigned mask = a.t.cap_mask[kind];
-    unsigned i = vpq_hash(key) & mask;
-    for (unsigned probe = 0; probe <= mask; ++probe, i = (i + 1) & mask) {
-        long long cur = __hip_atomic_load(keys + i, __ATOMIC_RELAXED, SC);
-        if (cur == -1) {
-            long long expect = -1;
-            if (__hip_atomic_compare_exchange_strong(keys + i, &expect, (long long)key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, SC))
-                cur = (long long)key;
-            else
-                cur = expect;                        // another wave took the slot: perhaps with this very key
-        }
-        if (cur == (long long)key) {
-            __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(base + a.t.counts[kind]) + i, cnt, __ATOMIC_RELAXED, SC);
-            return;
-        }
-    }
-    __hip_atomic_fetch_or(a.header, a.t.full_bit[kind], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // full: the count is dropped
+    mapcount::table_add<SC, VpqLds>(base + a.t.keys[kind], reinterpret_cast<unsigned long long*>(base + a.t.counts[kind]), a.t.cap_mask[kind], key, cnt, a.header,
+                                    a.t.full_bit[kind]);
 }
 
-__device__ void vpq_table_add(const VpqArgs& a, long long* base, int kind, unsigned long long key, unsigned long long cnt) {
-    vpq_table_add_t<__HIP_MEMORY_SCOPE_AGENT>(a, base, kind, key, cnt);
+__device__ void VpqLds::sink(const VpqLds& s, int kind, unsigned long long key, unsigned cnt) {
+    vpq_table_add_t<__HIP_MEMORY_SCOPE_AGENT>(s.a, s.slot, kind, key, cnt);
 }
 
-// the slot of a key in a set of tables, -1 when it is not there (its count was dropped by a full table)
+// the slot of a key in a set of tables, -1 when it is not there (its count was dropped by a full table): mapcount::table_add's probes
 template <int SC>
 __device__ __forceinline__ int vpq_table_find(const VpqArgs& a, long long* base, int kind, unsigned long long key) {
     long long* keys = base + a.t.keys[kind];
     const unsigned mask = a.t.cap_mask[kind];
-    unsigned i = vpq_hash(key) & mask;
+    unsigned i = VpqLds::hash(key) & mask;
     for (unsigned probe = 0; probe <= mask; ++probe, i = (i + 1) & mask) {
         const long long cur = __hip_atomic_load(keys + i, __ATOMIC_RELAXED, SC);
         if (cur == (long long)key) return (int)i;
@@ -193,62 +176,7 @@ __global__ __launch_bounds__(256) void k_vpq_clear(VpqArgs a, int done, int n) {
 }
 
 // ----------------------------------------------------------------------------------------------------------------------- count
-struct VpqLds {
-    unsigned long long keys[VKN_VPQ_LDS_SLOTS];
-    unsigned counts[VKN_VPQ_LDS_SLOTS];
-    VpqArgs a;                        // the launch's arguments: the out-of-line helpers index its tables by kind
-    long long* slot;                  // the frame's ring slot
-    unsigned flags;
-};
-
-// one tagged (key, count) into the workgroup's table
-__device__ void vpq_lds_add(VpqLds& s, unsigned long long tagged, unsigned cnt) {
-    unsigned i = vpq_hash(tagged) & (VKN_VPQ_LDS_SLOTS - 1);
-    for (int probe = 0; probe < VPQ_LDS_PROBES; ++probe, i = (i + 1) & (VKN_VPQ_LDS_SLOTS - 1)) {
-        const unsigned long long old = atomicCAS(&s.keys[i], VPQ_EMPTY, tagged);
-        if (old == VPQ_EMPTY || old == tagged) {
-            atomicAdd(&s.counts[i], cnt);
-            return;
-        }
-    }
-    vpq_table_add(s.a, s.slot, (int)(tagged & 3), tagged >> 2, cnt);
-}
-
-// Lanes that hand on a count at the same point: the lanes that hold the first such lane's key are summed (a lane's count has
-// VPQ_CNT_BITS bits: one ballot per bit) and that lane alone adds the sum; the others add their own.
-__device__ __forceinline__ void vpq_emit(VpqLds& s, bool e, unsigned long long tagged, unsigned cnt) {
-    if (e) {
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)tagged), hi = __builtin_amdgcn_readfirstlane((unsigned)(tagged >> 32));
-        const bool match = tagged == (((unsigned long long)hi << 32) | lo);
-        const unsigned long long mm = __ballot(match);
-        unsigned sum = 0;
-#pragma unroll
-        for (int b = 0; b < VPQ_CNT_BITS; ++b) sum += (unsigned)__popcll(__ballot(match && ((cnt >> b) & 1))) << b;
-        const int lane = threadIdx.x & 63;
-        if (match) {
-            if (lane == __ffsll((long long)mm) - 1) vpq_lds_add(s, tagged, sum);
-        } else {
-            vpq_lds_add(s, tagged, cnt);
-        }
-    }
-}
-
-struct VpqRun {
-    unsigned long long key;
-    unsigned cnt;
-};
-
-__device__ __forceinline__ void vpq_push(VpqLds& s, VpqRun& r, bool valid, unsigned long long tagged) {
-    const bool change = valid && r.key != tagged;
-    vpq_emit(s, change && r.cnt > 0, r.key, r.cnt);
-    if (change) {
-        r.key = tagged;
-        r.cnt = 0;
-    }
-    r.cnt += valid ? 1u : 0u;
-}
-
-__device__ __forceinline__ void vpq_pixel(VpqLds& s, const VpqArgs& a, VpqRun (&run)[3], unsigned& flags, int gs, int gi, int ps, int pi) {
+__device__ __forceinline__ void VpqLds::pixel(VpqLds& s, const VpqArgs& a, mapcount::Run (&run)[3], unsigned& flags, int gs, int gi, int ps, int pi) {
     const bool bad_class = (unsigned)ps >= (unsigned)a.num_cat || ((unsigned)gs >= (unsigned)a.num_cat && gs != a.ign);
     const bool bad_id = ((unsigned)gi >> a.shift) != 0 || ((unsigned)pi >> a.shift) != 0;      // negative ids have the top bit set
     if (bad_class) flags |= VKN_VPQ_STATUS_CLASS_RANGE;
@@ -256,9 +184,9 @@ __device__ __forceinline__ void vpq_pixel(VpqLds& s, const VpqArgs& a, VpqRun (&
     const bool live = !bad_class && !bad_id;
     const unsigned long long yt = live ? ((unsigned long long)(unsigned)gs << a.shift) + (unsigned)gi : 0ull;
     const unsigned long long yp = live ? ((unsigned long long)(unsigned)ps << a.shift) + (unsigned)pi : 0ull;
-    vpq_push(s, run[K_PRED], live, (yp << 2) | K_PRED);
-    vpq_push(s, run[K_GT], live, (yt << 2) | K_GT);
-    vpq_push(s, run[K_PAIR], live, ((yt * (unsigned long long)a.offset + yp) << 2) | K_PAIR);
+    mapcount::push(s, run[K_PRED], live, (yp << 2) | K_PRED);
+    mapcount::push(s, run[K_GT], live, (yt << 2) | K_GT);
+    mapcount::push(s, run[K_PAIR], live, ((yt * (unsigned long long)a.offset + yp) << 2) | K_PAIR);
 }
 
 // grid: n * wpf workgroups, wpf per frame of the group; a workgroup walks `per` neighbouring spans of ITS frame and keeps its table in LDS
@@ -269,10 +197,7 @@ __global__ __launch_bounds__(VPQ_THREADS) void k_vpq_count(VpqArgs a, const int*
     __shared__ VpqLds s;
     const int tid = threadIdx.x;
     const int j = blockIdx.x / wpf, chunk = blockIdx.x - j * wpf;
-    for (int i = tid; i < VKN_VPQ_LDS_SLOTS; i += VPQ_THREADS) {
-        s.keys[i] = VPQ_EMPTY;
-        s.counts[i] = 0;
-    }
+    mapcount::clear(s);
     if (tid == 0) {
         s.flags = 0;
         s.a = a;
@@ -282,50 +207,15 @@ __global__ __launch_bounds__(VPQ_THREADS) void k_vpq_count(VpqArgs a, const int*
 
     unsigned flags = 0;
     const size_t base = (size_t)(done + j) * HW;
-    const int* m0 = gt_sem + base;
-    const int* m1 = gt_ins + base;
-    const int* m2 = pred_sem + base;
-    const int* m3 = pred_ins + base;
     const int first = chunk * per, last = min(spans, first + per);
     for (int sp = first; sp < last; ++sp) {
         const int p0 = sp * VKN_VPQ_SPAN_PX, p1 = min(HW, p0 + VKN_VPQ_SPAN_PX);
-        // the peel: pixels in front of gt_sem's first 16-byte boundary inside the span; a map that is aligned differently is loaded by words
-        const int mis = (int)((reinterpret_cast<uintptr_t>(m0 + p0) >> 2) & 3);
-        const int head = min((4 - mis) & 3, p1 - p0);
-        const int q0 = p0 + head, groups = (p1 - q0) >> 2, q1 = q0 + 4 * groups;
-        const bool v1 = ((reinterpret_cast<uintptr_t>(m1 + q0)) & 15) == 0, v2 = ((reinterpret_cast<uintptr_t>(m2 + q0)) & 15) == 0,
-                   v3 = ((reinterpret_cast<uintptr_t>(m3 + q0)) & 15) == 0;
-
-        VpqRun run[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) run[k] = VpqRun{VPQ_EMPTY, 0u};
-
-        // head and tail pixels (fewer than 4 each), one per lane
-        {
-            const int p = tid < head ? p0 + tid : q1 + (tid - head);
-            if (p < p1 && (tid < head || p >= q1)) vpq_pixel(s, a, run, flags, m0[p], m1[p], m2[p], m3[p]);
-        }
-        for (int g = tid; g < groups; g += VPQ_THREADS) {
-            const int p = q0 + 4 * g;
-            const int4 x0 = *reinterpret_cast<const int4*>(m0 + p);
-            const int4 x1 = v1 ? *reinterpret_cast<const int4*>(m1 + p) : make_int4(m1[p], m1[p + 1], m1[p + 2], m1[p + 3]);
-            const int4 x2 = v2 ? *reinterpret_cast<const int4*>(m2 + p) : make_int4(m2[p], m2[p + 1], m2[p + 2], m2[p + 3]);
-            const int4 x3 = v3 ? *reinterpret_cast<const int4*>(m3 + p) : make_int4(m3[p], m3[p + 1], m3[p + 2], m3[p + 3]);
-            vpq_pixel(s, a, run, flags, x0.x, x1.x, x2.x, x3.x);
-            vpq_pixel(s, a, run, flags, x0.y, x1.y, x2.y, x3.y);
-            vpq_pixel(s, a, run, flags, x0.z, x1.z, x2.z, x3.z);
-            vpq_pixel(s, a, run, flags, x0.w, x1.w, x2.w, x3.w);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) vpq_emit(s, run[k].cnt > 0, run[k].key, run[k].cnt);      // per span: a lane's count stays in VPQ_CNT_BITS
+        mapcount::walk(s, a, flags, gt_sem + base, gt_ins + base, pred_sem + base, pred_ins + base, p0, p1);
     }
     if (flags) atomicOr(&s.flags, flags);
     __syncthreads();
 
-    for (int i = tid; i < VKN_VPQ_LDS_SLOTS; i += VPQ_THREADS) {
-        const unsigned long long tagged = s.keys[i];
-        if (tagged != VPQ_EMPTY) vpq_table_add(s.a, s.slot, (int)(tagged & 3), tagged >> 2, s.counts[i]);
-    }
+    mapcount::flush(s);
     if (tid == 0) {
         if (s.flags) __hip_atomic_fetch_or(a.header, s.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // the call's last group: nothing reads `frames` any more in this call (the windows read the latched base)
@@ -510,8 +400,8 @@ int vkn_vpq_reset(const VknVpqCfg* cfg, void* state, size_t state_bytes, void* s
     if (rc != VKN_OK) return rc;
     const VpqLayout l = vpq_layout(cfg);
     if (state_bytes != l.bytes) return VKN_E_WORKSPACE;
-    if (!vpq_aligned(state, 16)) return VKN_E_ALIGN;
-    if (!vpq_on_device(state)) return VKN_E_ARG;
+    if (!vkn_aligned(state, 16)) return VKN_E_ALIGN;
+    if (!vkn_on_device(state)) return VKN_E_ARG;
     // all zero: the ring slots and the windows' scratch are emptied by the kernels that use them
     if (hipMemsetAsync(state, 0, l.bytes, static_cast<hipStream_t>(stream)) != hipSuccess) return VKN_E_LAUNCH;
     return VKN_OK;
@@ -525,9 +415,9 @@ int vkn_vpq_update_i32(const VknVpqCfg* cfg, void* state, size_t state_bytes, co
     if (B < 1 || HW < 1 || (long long)B * HW * 4 >= (1ll << 31)) return VKN_E_SHAPE;
     const VpqLayout l = vpq_layout(cfg);
     if (state_bytes != l.bytes) return VKN_E_WORKSPACE;
-    if (!vpq_aligned(state, 16) || !vpq_aligned(gt_sem, 4) || !vpq_aligned(gt_ins, 4) || !vpq_aligned(pred_sem, 4) || !vpq_aligned(pred_ins, 4))
+    if (!vkn_aligned(state, 16) || !vkn_aligned(gt_sem, 4) || !vkn_aligned(gt_ins, 4) || !vkn_aligned(pred_sem, 4) || !vkn_aligned(pred_ins, 4))
         return VKN_E_ALIGN;
-    if (!vpq_on_device(state) || !vpq_on_device(gt_sem) || !vpq_on_device(gt_ins) || !vpq_on_device(pred_sem) || !vpq_on_device(pred_ins))
+    if (!vkn_on_device(state) || !vkn_on_device(gt_sem) || !vkn_on_device(gt_ins) || !vkn_on_device(pred_sem) || !vkn_on_device(pred_ins))
         return VKN_E_ARG;
     char* base = static_cast<char*>(state);
     VpqArgs a;

@@ -1487,6 +1487,15 @@ def localization_fpn(p2, p3, p4, p5, pos5, images, gammas, betas, groups):
     return loc, sem
 
 
+def _four_maps(who, state, gt_sem, gt_ins, pred_sem, pred_ins):
+    """(maps, B, HW) of a map meter's update: four int32 tensors [H,W] or [B,H,W] of one shape on the state's device."""
+    maps = [_req_plain(m, name, torch.int32) for m, name in zip((gt_sem, gt_ins, pred_sem, pred_ins), ('gt_sem', 'gt_ins', 'pred_sem', 'pred_ins'))]
+    shape = tuple(maps[0].shape)
+    if len(shape) not in (2, 3) or any(tuple(m.shape) != shape or m.device != state.device for m in maps):
+        raise ValueError(f'{who}: four int32 maps [H,W] or [B,H,W] of one shape on the state\'s device, got {[tuple(m.shape) for m in maps]}')
+    return maps, (shape[0] if len(shape) == 3 else 1), shape[-2] * shape[-1]
+
+
 # ---- the STQ meter (include/vkn_stq.h): one caller-owned state per sequence
 def stq_cfg(num_classes, ignore_label, label_bit_shift, offset, drop_ignored_gt=True, cap_gt=2048, cap_pred=8192, cap_pair=32768):
     """The `VknStqCfg` of a meter; raises VknError (VKN_E_SHAPE) outside the envelope of include/vkn_stq.h."""
@@ -1521,12 +1530,7 @@ def stq_reset(cfg, state):
 def stq_update(cfg, state, is_thing, gt_sem, gt_ins, pred_sem, pred_ins):
     """Count B frames of one sequence into `state` (vkn_stq_update_i32, one launch, no synchronisation).  The four maps: int32 CUDA
     tensors [H,W] or [B,H,W] of one shape; is_thing uint8 [n]."""
-    maps = [_req_plain(m, name, torch.int32) for m, name in zip((gt_sem, gt_ins, pred_sem, pred_ins), ('gt_sem', 'gt_ins', 'pred_sem', 'pred_ins'))]
-    shape = tuple(maps[0].shape)
-    if len(shape) not in (2, 3) or any(tuple(m.shape) != shape or m.device != state.device for m in maps):
-        raise ValueError(f'stq_update: four int32 maps [H,W] or [B,H,W] of one shape on the state\'s device, got {[tuple(m.shape) for m in maps]}')
-    B = shape[0] if len(shape) == 3 else 1
-    HW = shape[-2] * shape[-1]
+    maps, B, HW = _four_maps('stq_update', state, gt_sem, gt_ins, pred_sem, pred_ins)
     thing = _req_plain(is_thing, 'is_thing', torch.uint8)
     if thing.numel() < cfg.num_classes or thing.device != state.device:
         raise ValueError(f'stq_update: is_thing must hold at least num_classes = {cfg.num_classes} bytes on the state\'s device')
@@ -1573,11 +1577,6 @@ def vpq_reset(cfg, state):
 def vpq_update(cfg, state, gt_sem, gt_ins, pred_sem, pred_ins):
     """Count B consecutive frames of one sequence into `state` and close every window that ends in them (vkn_vpq_update_i32, three
     launches per VKN_VPQ_GROUP frames, no synchronisation).  The four maps: int32 CUDA tensors [H,W] or [B,H,W] of one shape."""
-    maps = [_req_plain(m, name, torch.int32) for m, name in zip((gt_sem, gt_ins, pred_sem, pred_ins), ('gt_sem', 'gt_ins', 'pred_sem', 'pred_ins'))]
-    shape = tuple(maps[0].shape)
-    if len(shape) not in (2, 3) or any(tuple(m.shape) != shape or m.device != state.device for m in maps):
-        raise ValueError(f'vpq_update: four int32 maps [H,W] or [B,H,W] of one shape on the state\'s device, got {[tuple(m.shape) for m in maps]}')
-    B = shape[0] if len(shape) == 3 else 1
-    HW = shape[-2] * shape[-1]
+    maps, B, HW = _four_maps('vpq_update', state, gt_sem, gt_ins, pred_sem, pred_ins)
     with torch.cuda.device(state.device):
         check(_lib.lib().vkn_vpq_update_i32(ctypes.byref(cfg), _ptr(state), state.numel(), *[_ptr(m) for m in maps], int(B), int(HW), _stream()))

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from ._map_meter import MapMeter
 
 _BITS = (('VKN_STQ_STATUS_ID_RANGE', 'ID_RANGE: an instance id outside [0, 2^label_bit_shift)'),
          ('VKN_STQ_STATUS_CLASS_RANGE', 'CLASS_RANGE: a class outside the confusion matrix'),
@@ -18,11 +19,12 @@ _BITS = (('VKN_STQ_STATUS_ID_RANGE', 'ID_RANGE: an instance id outside [0, 2^lab
 _EPSILON = 1e-15
 
 
-class STQMeter:
+class STQMeter(MapMeter):
     """num_classes, things_list, ignore_label, label_bit_shift, offset: `STQuality`'s arguments, and its ValueError for a small offset.
     drop_ignored_gt=True: pixels whose gt class is `ignore_label` do not exist, as the evaluation scripts mask them; False: `STQuality`
     on unmasked maps.  capacity: slots (powers of two, 16 .. 2^20) of the tube and intersection tables of ONE sequence; a table that
     overflows is reported by `result()` / `check_status()`, never silently."""
+    _BITS, _CONSTS, _new_state = _BITS, _lib.STQ, staticmethod(ops.stq_state)
 
     def __init__(self, num_classes, things_list, ignore_label, label_bit_shift, offset, drop_ignored_gt=True, capacity=None, device=None):
         lower_bound = num_classes << label_bit_shift
@@ -38,9 +40,7 @@ class STQMeter:
             raise ValueError(f'capacity takes the keys gt, pred, pair, got {sorted(cap)}')
         self.num_classes, self.ignore_label, self.label_bit_shift, self.offset = int(num_classes), int(ignore_label), int(label_bit_shift), int(offset)
         self.things_list, self.drop_ignored_gt, self.capacity = things, bool(drop_ignored_gt), cap
-        self.device = torch.device(device if device is not None else 'cuda')
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
+        super().__init__(device)
         self._cfg = ops.stq_cfg(num_classes, ignore_label, label_bit_shift, offset, drop_ignored_gt, cap['gt'], cap['pred'], cap['pair'])
         self._bytes, self._off = ops.stq_layout(self._cfg)
         self.n = num_classes + 1 if ignore_label >= num_classes else num_classes
@@ -51,19 +51,12 @@ class STQMeter:
         thing = np.zeros((self.n,), dtype=np.uint8)
         thing[things] = 1
         self._is_thing = torch.from_numpy(thing).to(self.device)
-        self._states = {}                                   # sequence id -> device state, in order of first appearance
 
     # ---- counting: device only
     def update_state(self, gt_sem, gt_ins, pred_sem, pred_ins, sequence_id=0):
         """int32 CUDA maps [H,W] or [B,H,W]: frames of ONE sequence.  pred_sem / pred_ins: `TrackTail`'s semantic_map / track_map as
         they come.  Enqueues one launch on the current stream; nothing is read back."""
-        state = self._states.get(sequence_id)
-        if state is None:
-            state = self._states[sequence_id] = ops.stq_state(self._cfg, self.device)
-        ops.stq_update(self._cfg, state, self._is_thing, gt_sem, gt_ins, pred_sem, pred_ins)
-
-    def reset_states(self):
-        self._states = {}
+        ops.stq_update(self._cfg, self._state(sequence_id), self._is_thing, gt_sem, gt_ins, pred_sem, pred_ins)
 
     # ---- reading: one device -> host copy per state
     def _host(self, sequence_id):
@@ -83,19 +76,6 @@ class STQMeter:
         """dict(confusion int64 [n,n] as accumulated, gt_keys / gt_counts, pred_keys / pred_counts, pair_keys / pair_counts sorted by key,
         status, frames) of one sequence."""
         return self._host(sequence_id)
-
-    @staticmethod
-    def _status_text(status):
-        return '; '.join(text for name, text in _BITS if status & _lib.STQ[name])
-
-    def _raise_on(self, sequence_id, status):
-        if status:
-            raise _lib.VknError(_lib.CONSTS['VKN_E_RANGE'], f'STQMeter: sequence {sequence_id!r}: status {status:#x}: {self._status_text(status)}')
-
-    def check_status(self):
-        """Raises VknError when any sequence's status word is set (reads 4 bytes per sequence: a synchronisation)."""
-        for sid, state in self._states.items():
-            self._raise_on(sid, int(state[0:4].cpu().numpy().view(np.uint32)[0]))
 
     def result(self):
         """`STQuality.result()` (STQ.py:190-283) in float64 from the device tables; the same eight entries.  AQ is summed over the

@@ -12,9 +12,9 @@ window of that k (eval_dvpq_vipseg.py:441 shortens k instead, for that sequence 
 import warnings
 
 import numpy as np
-import torch
 
 from . import _lib, ops
+from ._map_meter import MapMeter
 
 _BITS = (('VKN_VPQ_STATUS_ID_RANGE', 'ID_RANGE: an instance id outside [0, 2^label_bit_shift)'),
          ('VKN_VPQ_STATUS_CLASS_RANGE', 'CLASS_RANGE: a class outside the bins'),
@@ -25,11 +25,12 @@ _BITS = (('VKN_VPQ_STATUS_ID_RANGE', 'ID_RANGE: an instance id outside [0, 2^lab
 _EPSILON = 1e-10
 
 
-class VPQMeter:
+class VPQMeter(MapMeter):
     """num_classes: the bins are num_classes + 1 (`num_cat`: 20 for STEP, 125 for VIP-Seg); things_list: the thing classes of
     PQ_thing / PQ_stuff; ks: window lengths, ascending (`--eval_frames`; (1, 2, 4, 6) in the VIP-Seg script); ign_id, label_bit_shift,
     offset: the scripts' constants.  capacity: slots (powers of two, 16 .. 2^20) of the gt / pred / pair tables of ONE frame and of ONE
     window, and records of the TP log of one sequence; what overflows is reported by `result()` / `check_status()`, never silently."""
+    _BITS, _CONSTS, _new_state = _BITS, _lib.VPQ, staticmethod(ops.vpq_state)
 
     def __init__(self, num_classes, things_list, ks=(1,), ign_id=255, label_bit_shift=16, offset=2 ** 30, capacity=None, device=None):
         things = sorted({int(c) for c in things_list})
@@ -42,24 +43,15 @@ class VPQMeter:
         self.num_classes, self.num_cat, self.ks = int(num_classes), int(num_classes) + 1, tuple(int(k) for k in ks)
         self.ign_id, self.label_bit_shift, self.offset = int(ign_id), int(label_bit_shift), int(offset)
         self.things_list, self.capacity = things, cap
-        self.device = torch.device(device if device is not None else 'cuda')
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
+        super().__init__(device)
         self._cfg = ops.vpq_cfg(self.num_cat, self.ks, ign_id, label_bit_shift, offset, cap['gt'], cap['pred'], cap['pair'], cap['log'])
         self._bytes, self._off = ops.vpq_layout(self._cfg)
-        self._states = {}                                   # sequence id -> device state, in order of first appearance
 
     # ---- counting: device only
     def update_state(self, gt_sem, gt_ins, pred_sem, pred_ins, sequence_id=0):
         """int32 CUDA maps [H,W] or [B,H,W]: CONSECUTIVE frames of ONE sequence, behind the frames of earlier calls.  pred_sem / pred_ins:
         `TrackTail`'s semantic_map / track_map as they come.  Enqueues on the current stream; nothing is read back."""
-        state = self._states.get(sequence_id)
-        if state is None:
-            state = self._states[sequence_id] = ops.vpq_state(self._cfg, self.device)
-        ops.vpq_update(self._cfg, state, gt_sem, gt_ins, pred_sem, pred_ins)
-
-    def reset_states(self):
-        self._states = {}
+        ops.vpq_update(self._cfg, self._state(sequence_id), gt_sem, gt_ins, pred_sem, pred_ins)
 
     # ---- reading: the public parts of a state, one device -> host copy
     def _host(self, sequence_id):
@@ -75,19 +67,6 @@ class VPQMeter:
         """dict(acc int64 [nk, 3, num_cat]: tp, fn, fp per window length; log int64 [n, 4] sorted by its first two fields:
         (k_index << 48) | window_ordinal, pair key, int_area, union; frames; status) of one sequence."""
         return self._host(sequence_id)
-
-    @staticmethod
-    def _status_text(status):
-        return '; '.join(text for name, text in _BITS if status & _lib.VPQ[name])
-
-    def _raise_on(self, sequence_id, status):
-        if status:
-            raise _lib.VknError(_lib.CONSTS['VKN_E_RANGE'], f'VPQMeter: sequence {sequence_id!r}: status {status:#x}: {self._status_text(status)}')
-
-    def check_status(self):
-        """Raises VknError when any sequence's status word is set (reads 4 bytes per sequence: a synchronisation)."""
-        for sid, state in self._states.items():
-            self._raise_on(sid, int(state[0:4].cpu().numpy().view(np.uint32)[0]))
 
     def _counts(self, hosts):
         nk, nc, shift = len(self.ks), self.num_cat, self.label_bit_shift
