@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libvkn.so')
-SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_segloss.hip', 'vkn_stq.hip', 'vkn_vpq.hip', 'vkn_api.hip')
+SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_segloss.hip', 'vkn_stq.hip', 'vkn_vpq.hip', 'vkn_fpn_bwd.hip', 'vkn_api.hip')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 # The C ABI, one header per part, each behind the headers it #includes.  A new part is one more name here.
 ABI_HEADERS = ('vkn.h', 'vkn_track.h', 'vkn_track_train.h', 'vkn_gt.h', 'vkn_decode.h')
@@ -27,6 +27,8 @@ EXTENSION_HEADERS = ('vkn_seg_loss.h',)
 METRIC_HEADERS = ('vkn_stq.h',)
 # Windowed metric parts: a fourth such table `ABI_WINDOW_METRIC` behind the three, on the same terms; its constants in their own record `VPQ`.
 WINDOW_METRIC_HEADERS = ('vkn_vpq.h',)
+# Training parts: a fifth such table `ABI_TRAIN` behind the four, on the same terms; its constants in their own record `FPN_TRAIN`.
+TRAIN_HEADERS = ('vkn_fpn_train.h',)
 
 
 class VknLibraryError(RuntimeError):
@@ -131,20 +133,22 @@ def read_abi(include_dir, names):
 
 
 def _each(field, tables=None):
-    """[(header, name, value)] of one field of every header's record — `ABI`'s, then `ABI_EXT`'s, `ABI_METRIC`'s, `ABI_WINDOW_METRIC`'s — in the headers' order"""
-    return [(h, k, v) for t in (tables or (ABI, ABI_EXT, ABI_METRIC, ABI_WINDOW_METRIC)) for h, hdr in t.items() for k, v in getattr(hdr, field).items()]
+    """[(header, name, value)] of one field of every header's record — `ABI`'s, then `ABI_EXT`'s, `ABI_METRIC`'s, `ABI_WINDOW_METRIC`'s, `ABI_TRAIN`'s — in the headers' order"""
+    return [(h, k, v) for t in (tables or (ABI, ABI_EXT, ABI_METRIC, ABI_WINDOW_METRIC, ABI_TRAIN)) for h, hdr in t.items() for k, v in getattr(hdr, field).items()]
 
 
-_ALL = read_abi(INCLUDE, ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS)          # ONE reading: includes resolve, a name declared twice is an error
+_ALL = read_abi(INCLUDE, ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS + TRAIN_HEADERS)          # ONE reading: includes resolve, a name declared twice is an error
 ABI = {h: _ALL[h] for h in ABI_HEADERS}
 ABI_EXT = {h: _ALL[h] for h in EXTENSION_HEADERS}
 ABI_METRIC = {h: _ALL[h] for h in METRIC_HEADERS}
 ABI_WINDOW_METRIC = {h: _ALL[h] for h in WINDOW_METRIC_HEADERS}
+ABI_TRAIN = {h: _ALL[h] for h in TRAIN_HEADERS}
 HEADER, PROTOS, SYMBOLS, STRUCTS, MIRRORS = (getattr(ABI['vkn.h'], k) for k in ('path', 'protos', 'symbols', 'structs', 'mirrors'))
 CONSTS = {k: v for _, k, v in _each('consts', (ABI,))}      # every ABI header's constants: no name is declared twice
 SEG = ABI_EXT['vkn_seg_loss.h'].consts              # an extension's constants stay in its own record
 STQ = ABI_METRIC['vkn_stq.h'].consts                # ... and so do a metric part's
 VPQ = ABI_WINDOW_METRIC['vkn_vpq.h'].consts         # ... and a windowed metric part's
+FPN_TRAIN = ABI_TRAIN['vkn_fpn_train.h'].consts     # ... and a training part's
 GT_MAX_IMAGES = CONSTS['VKN_GT_MAX_IMAGES']
 GT_MAX_CLASSES = CONSTS['VKN_GT_MAX_CLASSES']
 GT_MAX_IDS = CONSTS['VKN_GT_MAX_IDS']
@@ -189,7 +193,7 @@ POINTER_EXCEPTIONS = {
     ('vkn_vpq_state_layout', 'offsets4'): ctypes.POINTER(ctypes.c_size_t),          # likewise, (c_size_t * 4)()
 }
 for _fn, _p in set(POINTER_EXCEPTIONS) - {(fn, q[0]) for _, fn, (_, params) in _each('protos') for q in params}:
-    raise VknLibraryError(f'POINTER_EXCEPTIONS names {_fn}({_p}), which none of the headers {ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS} declares')
+    raise VknLibraryError(f'POINTER_EXCEPTIONS names {_fn}({_p}), which none of the headers {ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS + TRAIN_HEADERS} declares')
 
 DEBUG_LIBPATH = os.path.join(LIBDIR, 'libvkn_debug.so')
 

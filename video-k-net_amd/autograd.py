@@ -417,3 +417,38 @@ def seg_loss(low, tgt, dense_pos, mode, stride, alpha=0.25, gamma=2.0, loss_weig
     """low fp32 [B,ncls,h,w]; tgt uint8 [B,S h,S w] and dense_pos int32 [1] of `ops.seg_targets`; mode `ops.SEG_LOSS_FOCAL` / `_CE`
     -> the loss as a 0-d tensor."""
     return SegLossFn.apply(low, tgt, dense_pos, mode, stride, alpha, gamma, loss_weight)
+
+
+class ConvGNReLUFn(torch.autograd.Function):
+    """One mmcv `ConvModule`, y = ReLU(GN(conv(x))) with a k x k conv (k = weight.shape[-1], padding k // 2, no bias), forward and
+    backward on the library's kernels (include/vkn_fpn_train.h) from a materialised fp32 input.  Forward: `vkn_conv_gn_f32` in its
+    raw-input mode, then the GroupNorm + ReLU pass; x, the raw conv output and its statistics are saved.  Backward: the GroupNorm +
+    ReLU backward, the weight gradient, and — only when x needs one — the input gradient.  A non-finite gradient is reported through
+    `ops.workspace_status`."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, groups, stride):
+        x = x.contiguous()
+        Cout, _, k, _ = weight.shape
+        r, stats = ops.conv_gn(x, ops.conv_prepare(weight), Cout, k, stride, groups)
+        ctx.save_for_backward(x, weight, gamma, beta, r, stats)
+        ctx.stride = stride
+        ctx.ws_cache = ops.workspace_cache()      # the backward reports into the status word of the thread that ran the forward
+        return ops.gn_relu_apply(r, stats, gamma, beta)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, gamma, beta, r, stats = ctx.saved_tensors
+        k, stride = weight.shape[-1], ctx.stride
+        with ops.adopt_workspace(ctx.ws_cache):
+            dr, dgamma, dbeta = ops.gn_relu_bwd(dy.contiguous(), r, stats, gamma, beta)
+            dw = ops.conv_wgrad(dr, x, k, stride) if ctx.needs_input_grad[1] else None
+            dx = None
+            if ctx.needs_input_grad[0]:
+                image_t = ops.conv_prepare(weight.detach().flip(2, 3).transpose(0, 1).contiguous())
+                dx = ops.conv_dgrad(dr, image_t, x.shape[1], x.shape[2], x.shape[3], k, stride)
+        return dx, dw, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None, None, None
+
+
+def conv_gn_relu(x, weight, gamma, beta, groups, stride=1):
+    return ConvGNReLUFn.apply(x, weight, gamma, beta, groups, stride)

@@ -4,6 +4,7 @@ Every function enqueues HIP kernels of libvkn.so on the CURRENT torch stream, on
 torch tensors.  Inputs must be CUDA(=HIP) fp32 tensors; there is no CPU path here by design — the CPU restatement
 lives in `oracle/` and is test infrastructure only.
 """
+import contextlib
 import ctypes
 import struct
 import threading
@@ -93,6 +94,28 @@ def _workspace(nbytes, device, scratch=False):
             gen = _tls.ws_gen = {}
         gen[key] = gen.get(key, 0) + 1   # `workspace_generation`: state kept in the buffer between calls (PHASE_A/B/C) dies with a regrow
     return buf[256:] if scratch else buf
+
+
+def workspace_cache():
+    """This thread's workspace cache (one buffer per (device, stream), with its status header) as a handle for `adopt_workspace`."""
+    if getattr(_tls, 'ws', None) is None:
+        _tls.ws = {}
+    if getattr(_tls, 'ws_gen', None) is None:
+        _tls.ws_gen = {}
+    return _tls.ws, _tls.ws_gen
+
+
+@contextlib.contextmanager
+def adopt_workspace(cache):
+    """Run the block on the workspace cache of ANOTHER thread (`workspace_cache()` taken there).  autograd runs a backward on a thread
+    of its own, on the forward's stream, while the thread that called it waits: a backward that adopts the forward thread's cache
+    ORs its status bits into the word that thread's `workspace_status` reads, instead of a header nobody looks at."""
+    old = getattr(_tls, 'ws', None), getattr(_tls, 'ws_gen', None)
+    _tls.ws, _tls.ws_gen = cache
+    try:
+        yield
+    finally:
+        _tls.ws, _tls.ws_gen = old
 
 
 def workspace_generation(device):
@@ -1485,6 +1508,86 @@ def localization_fpn(p2, p3, p4, p5, pos5, images, gammas, betas, groups):
         check(L.vkn_localization_fpn_f32(*[_ptr(p) for p in ps], _ptr(pos), arr(images), arr(gs), arr(bs), int(groups),
                                          _ptr(loc), _ptr(sem), B, C, *dims, _ptr(ws), ws.numel(), _stream()))
     return loc, sem
+
+
+# ---- backward of one conv + GroupNorm + ReLU block (include/vkn_fpn_train.h)
+def gn_relu_apply(r, stats, gamma, beta):
+    """y = relu(GN(r)) from a RAW conv output r [B, C, H, W] and the (mean, rstd) [B, groups, 2] that `conv_gn` returned with it
+    (include/vkn_fpn_train.h: vkn_gn_relu_apply_f32)."""
+    r, stats = _req(r, 'r'), _req(stats, 'stats')
+    B, C, H, W = r.shape
+    y = torch.empty_like(r)
+    with torch.cuda.device(r.device):
+        check(_lib.lib().vkn_gn_relu_apply_f32(_ptr(r), _ptr(stats), _ptr(_req(gamma, 'gamma')), _ptr(_req(beta, 'beta')), stats.shape[1],
+                                               _ptr(y), B, C, H, W, _stream()))
+    return y
+
+
+def gn_relu_bwd(dy, r, stats, gamma, beta):
+    """(dr, dgamma, dbeta) of y = relu(GN(r)) from the gradient dy of y (vkn_gn_relu_bwd_f32): the ReLU mask is recomputed from r,
+    the sums are merged in a fixed order in fp64.  A non-finite dy is reported through `workspace_status`."""
+    dy, r, stats = _req(dy, 'dy'), _req(r, 'r'), _req(stats, 'stats')
+    if dy.shape != r.shape:
+        raise ValueError(f'gn_relu_bwd: dy {tuple(dy.shape)} and r {tuple(r.shape)} differ')
+    B, C, H, W = r.shape
+    G, dev = stats.shape[1], r.device
+    L = _lib.lib()
+    nb = L.vkn_gn_relu_bwd_workspace_bytes(B, C, H, W, G)
+    if not nb:
+        raise ValueError('gn_relu_bwd: shape outside the envelope')
+    dr = torch.empty_like(r)
+    dgamma = torch.empty(C, dtype=torch.float32, device=dev)
+    dbeta = torch.empty_like(dgamma)
+    ws = _workspace(nb, dev)
+    with torch.cuda.device(dev):
+        check(L.vkn_gn_relu_bwd_f32(_ptr(dy), _ptr(r), _ptr(stats), _ptr(_req(gamma, 'gamma')), _ptr(_req(beta, 'beta')), G, _ptr(dr),
+                                    _ptr(dgamma), _ptr(dbeta), B, C, H, W, _ptr(ws), ws.numel(), _stream()))
+    return dr, dgamma, dbeta
+
+
+def conv_wgrad(dr, x, ksize, stride=1):
+    """dW [Cout, Cin, k, k] of a conv (padding k // 2, no bias) from the gradient dr [B, Cout, Ho, Wo] of its raw output and its input
+    x [B, Cin, H, W] (vkn_conv_wgrad_f32): MFMA over B Ho Wo, both operands scaled by a power of two per tensor."""
+    dr, x = _req(dr, 'dr'), _req(x, 'x')
+    B, Cin, H, W = x.shape
+    Cout, dev = dr.shape[1], x.device
+    if tuple(dr.shape) != (B, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise ValueError(f'conv_wgrad: dr {tuple(dr.shape)} is not the output of x {tuple(x.shape)} at stride {stride}')
+    L = _lib.lib()
+    nb = L.vkn_conv_wgrad_workspace_bytes(B, Cin, H, W, Cout, int(ksize), int(stride))
+    if not nb:
+        raise ValueError('conv_wgrad: shape outside the envelope')
+    dw = torch.empty((Cout, Cin, ksize, ksize), dtype=torch.float32, device=dev)
+    ws = _workspace(nb, dev)
+    with torch.cuda.device(dev):
+        check(L.vkn_conv_wgrad_f32(_ptr(dr), _ptr(x), _ptr(dw), B, Cin, H, W, Cout, int(ksize), int(stride), _ptr(ws), ws.numel(), _stream()))
+    return dw
+
+
+def conv_dgrad(dr, image_t, Cin, H, W, ksize, stride=1):
+    """dx [B, Cin, H, W] of a conv from dr [B, Cout, Ho, Wo] (vkn_conv_dgrad_f32).  `image_t` is
+    `conv_prepare(weight.flip(2, 3).transpose(0, 1))`: the flipped, channel-transposed weight as the forward engine's A operand."""
+    dr = _req(dr, 'dr')
+    B, Cout = dr.shape[:2]
+    if tuple(dr.shape[2:]) != ((H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise ValueError(f'conv_dgrad: dr {tuple(dr.shape)} is not the output of a {H} x {W} input at stride {stride}')
+    L = _lib.lib()
+    nb = L.vkn_conv_dgrad_workspace_bytes(B, Cout, H, W, int(stride))
+    if not nb or image_t.numel() != L.vkn_conv_weight_bytes(int(Cin), Cout, int(ksize)):
+        raise ValueError('conv_dgrad: shape outside the envelope, or an image of another weight')
+    dev = dr.device
+    dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=dev)
+    ws = _workspace(nb, dev)
+    with torch.cuda.device(dev):
+        check(L.vkn_conv_dgrad_f32(_ptr(dr), _ptr(image_t), _ptr(dx), B, int(Cin), H, W, Cout, int(ksize), int(stride), _ptr(ws), ws.numel(),
+                                   _stream()))
+    return dx
+
+
+def conv_gn_relu_fits(Cin, Cout, ksize, stride, groups):
+    """The envelope of the block's forward and backward kernels (include/vkn_fpn_train.h)"""
+    return (Cin % 32 == 0 and Cout % 32 == 0 and 0 < Cin <= 512 and 0 < Cout <= 512 and groups > 0 and Cout % groups == 0
+            and (ksize, stride) in ((3, 1), (3, 2), (1, 1)))
 
 
 def _four_maps(who, state, gt_sem, gt_ins, pred_sem, pred_ins):

@@ -4,14 +4,16 @@ one (GN(32) + ReLU, positional encoding at level 3, upsample_times 2, one aux co
 
 Inference (no gradient needed) is ONE C-ABI call (`vkn_localization_fpn_f32`: implicit-GEMM 3x3 convs on MFMA, GroupNorm + ReLU
 applied on load by each consumer); with a gradient the module runs the plain torch composition of its own layers, so training works
-on the same parameters.
+on the same parameters.  With `fused_backward=True` (an extra keyword, off by default) that training forward runs every
+ConvModule inside the kernels' envelope through `autograd.ConvGNReLUFn`: conv + GroupNorm + ReLU forward and backward in HIP
+(include/vkn_fpn_train.h), the bilinear x2, the level sum and the positional add staying torch autograd ops.
 """
 import math
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import autograd, ops
 from .registry import HAVE_MM, HEADS
 
 
@@ -66,8 +68,10 @@ class SemanticFPNWrapper(nn.Module):
 
     def __init__(self, in_channels, feat_channels, out_channels, start_level, end_level, cat_coors=False, positional_encoding=None,
                  cat_coors_level=3, fuse_by_cat=False, return_list=False, upsample_times=3, with_pred=True, num_aux_convs=0,
-                 act_cfg=dict(type='ReLU', inplace=True), out_act_cfg=dict(type='ReLU'), conv_cfg=None, norm_cfg=None):
+                 act_cfg=dict(type='ReLU', inplace=True), out_act_cfg=dict(type='ReLU'), conv_cfg=None, norm_cfg=None,
+                 fused_backward=False):
         super().__init__()
+        self.fused_backward = bool(fused_backward)      # not the reference's: the training forward on the HIP block (forward_train_fused)
         assert start_level >= 0 and end_level >= start_level
         if cat_coors:
             _unsupported('cat_coors=True')
@@ -150,6 +154,36 @@ class SemanticFPNWrapper(nn.Module):
             return [out] + [conv(feat) for conv in self.aux_convs]
         return [out] if self.return_list else out
 
+    def _conv_modules(self):
+        return [m for m in self.modules() if isinstance(m, _ConvModule)]
+
+    def train_fused_ok(self, inputs):
+        """Every ConvModule inside the envelope of include/vkn_fpn_train.h, every input an fp32 tensor on the GPU"""
+        return (all(ops.conv_gn_relu_fits(m.conv.in_channels, m.conv.out_channels, m.conv.kernel_size[0], m.conv.stride[0], m.gn.num_groups)
+                    and m.conv.weight.is_cuda and m.conv.weight.dtype == torch.float32 for m in self._conv_modules())
+                and all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 for x in inputs[self.start_level:self.end_level + 1]))
+
+    @staticmethod
+    def _block(m, x):
+        return autograd.conv_gn_relu(x, m.conv.weight, m.gn.weight, m.gn.bias, m.gn.num_groups, m.conv.stride[0])
+
+    def forward_train_fused(self, inputs):
+        """`forward_torch` with every ConvModule as one `autograd.ConvGNReLUFn` (HIP forward and backward); `nn.Upsample`, the level
+        sum and the positional add are the same torch ops."""
+        mlvl = []
+        for i in range(self.start_level, self.end_level + 1):
+            x = inputs[i]
+            if i == self.cat_coors_level and self.positional_encoding is not None:
+                x = x + self.positional_map(x.shape[0], x.shape[-2], x.shape[-1], x.device).to(x.dtype)
+            for layer in self.convs_all_levels[i]:
+                x = self._block(layer, x) if isinstance(layer, _ConvModule) else layer(x)
+            mlvl.append(x)
+        feat = sum(mlvl)
+        out = self._block(self.conv_pred, feat) if self.with_pred else feat
+        if self.num_aux_convs > 0:
+            return [out] + [self._block(conv, feat) for conv in self.aux_convs]
+        return [out] if self.return_list else out
+
     def fused_ok(self):
         """The structure `vkn_localization_fpn_f32` implements: every shipped config's."""
         return (self.start_level == 0 and self.end_level == 3 and self.upsample_times == 2 and self.with_pred and self.num_aux_convs == 1
@@ -197,6 +231,8 @@ class SemanticFPNWrapper(nn.Module):
 
     def forward(self, inputs):
         if self._needs_grad(inputs):
+            if self.fused_backward and self.train_fused_ok(inputs):
+                return self.forward_train_fused(inputs)
             return self.forward_torch(inputs)
         if not self.fused_ok():
             raise NotImplementedError('SemanticFPNWrapper inference is built for the shipped structure (levels 0-3, upsample_times=2, '
