@@ -93,6 +93,29 @@ def test_raw_pos_unequal_channels_and_probes_bit_for_bit(vkn):
     _finish(vkn, [f for f in fails if f])
 
 
+def test_norm_on_load_is_the_apply_kernel_bit_for_bit(vkn):
+    """One pre-activation (csrc/vkn_convtile.h: gn_preact) behind the conv's load and behind vkn_gn_relu_apply_f32: a conv that
+    normalises a raw output r on load equals the same conv on the materialised relu(GN(r)), raw output and statistics, on float operands
+    (a pre-activation near zero rounded two ways would clip in one and not in the other).  One full 64-pixel run plus one pixel."""
+    ops = vkn.ops
+    g = _g(2300)
+    B, C, H, W, G = 1, 32, 3, 65, 8
+    x = torch.randn(B, C, H, W, generator=g)
+    w1, w2 = (0.05 * torch.randn(C, C, 3, 3, generator=g) for _ in range(2))
+    gamma = (0.5 + torch.rand(C, generator=g)) * (torch.randint(0, 2, (C,), generator=g) * 2 - 1)
+    beta = 0.3 * torch.randn(C, generator=g)
+    x, w1, w2, gamma, beta = _cuda(x, w1, w2, gamma, beta)
+    r, st = ops.conv_gn(x, ops.conv_prepare(w1), C, 3, 1, G)
+    img2 = ops.conv_prepare(w2)
+    y = ops.gn_relu_apply(r, st, gamma, beta)
+    assert 0.25 < float((y == 0).float().mean()) < 0.75 and bool((y > 0).any())          # the ReLU clips a good share, not all
+    on_load, on_load_st = ops.conv_gn(r, img2, C, 3, 1, G, in_stats=st, in_gamma=gamma, in_beta=beta)
+    applied, applied_st = ops.conv_gn(y, img2, C, 3, 1, G)
+    assert torch.equal(on_load, applied) and torch.equal(on_load_st, applied_st)
+    torch.cuda.synchronize()
+    ops.workspace_status()
+
+
 # ------------------------------------------------------------------------------------------------------------ 2. conditioned
 COND = [(mode, B, Ci, Co, H, W, ks, st) for (B, Ci, Co, H, W, ks, st) in ((2, 64, 96, 3, 65, 3, 1), (1, 256, 64, 5, 33, 3, 2), (1, 32, 512, 4, 64, 1, 1))
         for mode in ('raw', 'pos', 'norm')] + [('up', 2, 64, 96, 2, 33, 3, 1)]

@@ -20,7 +20,9 @@
 // Range: every staged activation must satisfy |v| < 65504 (the f16 split's envelope); a non-finite or larger value ORs
 // VKN_STATUS_RANGE into the workspace status word (include/vkn.h).
 #include "../../include/vkn.h"
+#include "../../include/vkn_fpn_train.h"
 #include "vkn_common.h"
+#include "vkn_convtile.h"
 
 #include <algorithm>
 
@@ -30,12 +32,7 @@
         if (rc_ != VKN_OK) return rc_; \
     } while (0)
 
-#define FPN_THREADS 256
-#define FPN_TILE 64   // output pixels per workgroup (one row run)
-#define FPN_KC 32     // input channels per staged chunk (two MFMA k-steps)
-#define FPN_PITCH 40  // halfs per patch column: 32 channels + 8 pad (80-byte stride, 16-byte aligned fragment reads)
 #define FPN_MAX_SRC 4
-#define FPN_IMG_HDR 256  // prepared image: {scale, 1 / scale} then the fragments from byte 256
 
 enum { FPN_RAW = 0, FPN_NORM = 1, FPN_UP = 2 };
 
@@ -63,7 +60,7 @@ struct FpnConvArgs {
 
 __device__ __forceinline__ float fpn_norm(const FpnSrc& s, int b, int c, float v) {
     const float* st = s.st + 2 * ((long long)b * s.gstride + c / s.cpg);
-    return fmaxf((v - st[0]) * st[1] * s.gamma[c] + s.beta[c], 0.f);
+    return fmaxf(convtile::gn_preact(v, st[0], st[1], s.gamma[c], s.beta[c]), 0.f);
 }
 
 // value of input channel c at conv-input position (iy, ix), inside [0, Hin) x [0, Win)
@@ -100,9 +97,10 @@ __device__ __forceinline__ float fpn_half_sum(float v) {
 #undef FPN_DPP_ADD
 
 template <int KS, int S>
-__global__ __launch_bounds__(FPN_THREADS) void k_fpn_conv(FpnConvArgs a) {
-    constexpr int XW = (FPN_TILE - 1) * S + KS;  // patch columns
-    constexpr int PL = KS * XW * FPN_PITCH;      // halfs per plane
+__global__ __launch_bounds__(convtile::THREADS) void k_fpn_conv(FpnConvArgs a) {
+    using namespace convtile;
+    constexpr int XW = (TILE - 1) * S + KS;  // patch columns
+    constexpr int PL = KS * XW * PITCH;      // halfs per plane
     extern __shared__ _Float16 fpn_lds[];
     _Float16* lhi = fpn_lds;
     _Float16* llo = fpn_lds + PL;
@@ -110,67 +108,34 @@ __global__ __launch_bounds__(FPN_THREADS) void k_fpn_conv(FpnConvArgs a) {
     const int tx = blockIdx.x, oy = blockIdx.y, b = blockIdx.z / ncog, cog = blockIdx.z % ncog;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int ncb = a.Cout >> 5, nks = a.Cin >> 4;
-    const int cb0 = cog * 8 + wave * 2;
-    const bool has0 = cb0 < ncb, has1 = cb0 + 1 < ncb;
-    const int ox0 = tx * FPN_TILE, iy0 = oy * S - KS / 2, ix0 = ox0 * S - KS / 2;
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int pb = 0; pb < 2; ++pb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[q][pb][r] = 0.f;
+    const WaveMap wm = wave_map(cog, wave, ncb);
+    const int cb0 = wm.cb0;
+    const int ox0 = tx * TILE, iy0 = oy * S - KS / 2, ix0 = ox0 * S - KS / 2;
+    f32x16 acc[2][2] = {};
     unsigned bad = 0;
     const half8* wimg = reinterpret_cast<const half8*>(a.wimg);
-    for (int c0 = 0; c0 < a.Cin; c0 += FPN_KC) {
-        for (int e = threadIdx.x; e < FPN_KC * KS * XW; e += FPN_THREADS) {
+    for (int c0 = 0; c0 < a.Cin; c0 += KC) {
+        for (int e = threadIdx.x; e < KC * KS * XW; e += THREADS) {
             const int j = e % XW, r = (e / XW) % KS, ci = e / (XW * KS);
             const int iy = iy0 + r, ix = ix0 + j;
             float v = 0.f;  // zero padding of the conv input
             if (iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win) v = fpn_load(a, b, c0 + ci, iy, ix);
-            bad |= !(fabsf(v) < 65504.f);
-            _Float16 h, l;
-            vkn_split_f16(v, h, l);
-            const int o = (r * XW + j) * FPN_PITCH + ci;
-            lhi[o] = h;
-            llo[o] = l;
+            stage(v, bad, lhi, llo, (r * XW + j) * PITCH + ci);
         }
         __syncthreads();
-        if (has0) {
+        if (wm.has0) {
 #pragma unroll
             for (int tap = 0; tap < KS * KS; ++tap) {
                 const int ky = tap / KS, kx = tap % KS;
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const int ks = (c0 >> 4) + s;
-                    half8 ah[2], al[2];
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        const int cb = has1 ? cb0 + q : cb0;
-                        const half8* p = wimg + ((((size_t)tap * nks + ks) * ncb + cb) * 2) * 64 + lane;
-                        ah[q] = p[0];
-                        al[q] = p[64];
-                    }
-#pragma unroll
-                    for (int pb = 0; pb < 2; ++pb) {
-                        const int o = (ky * XW + (pb * 32 + (lane & 31)) * S + kx) * FPN_PITCH + s * 16 + (lane >> 5) * 8;
-                        const half8 bh = *reinterpret_cast<const half8*>(lhi + o);
-                        const half8 bl = *reinterpret_cast<const half8*>(llo + o);
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            acc[q][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[q], bh, acc[q][pb], 0, 0, 0);
-                            acc[q][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[q], bl, acc[q][pb], 0, 0, 0);
-                            acc[q][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[q], bh, acc[q][pb], 0, 0, 0);
-                        }
-                    }
-                }
+                tap_product(acc, wimg, tap, nks, ncb, c0, cb0, wm.has1, lane, lhi, llo, (ky * XW + (lane & 31) * S + kx) * PITCH,
+                            32 * S * PITCH);
             }
         }
         __syncthreads();
     }
     if (bad) atomicOr(a.status, (unsigned)VKN_STATUS_RANGE);
     const float isc = a.wscale[1];
-    const int nvalid = min(FPN_TILE, a.Wo - ox0);
+    const int nvalid = min(TILE, a.Wo - ox0);
     const float inv_n = 1.f / (float)nvalid;
     const bool ok0 = (lane & 31) < nvalid, ok1 = 32 + (lane & 31) < nvalid;
     const long long P = (long long)a.Ho * a.Wo;
@@ -211,7 +176,7 @@ __global__ __launch_bounds__(256) void k_fpn_gn_finish(const float* __restrict__
     for (long long i = i0; i < i1; ++i) {
         const int c = g * cpg + (int)(i / T), t = (int)(i % T);
         const float* p = part + 2 * (((long long)b * Cout + c) * T + t);
-        const double nb = (double)min(FPN_TILE, Wo - (t % ntx) * FPN_TILE), mb = p[0], qb = p[1];
+        const double nb = (double)min(convtile::TILE, Wo - (t % ntx) * convtile::TILE), mb = p[0], qb = p[1];
         const double nn = n + nb, d = mb - m;
         m += d * nb / nn;
         q += qb + d * d * n * nb / nn;
@@ -240,39 +205,26 @@ __global__ __launch_bounds__(256) void k_fpn_gn_finish(const float* __restrict__
 }
 
 // y = relu(GN(x)) for C channels of a raw output (frame stride in_bstride) -> dst [B][C][P]; may run in place
-__global__ __launch_bounds__(256) void k_fpn_gn_apply(const float* __restrict__ x, long long in_bstride, const float* __restrict__ st,
+__global__ __launch_bounds__(256) void k_fpn_gn_apply(const float* x, long long in_bstride, const float* __restrict__ st,
                                                       int gstride, int cpg, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, float* dst, int C, long long P) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (long long)C * P; i += (long long)gridDim.x * 256) {
         const int b = blockIdx.y, c = (int)(i / P);
         const float* s = st + 2 * ((long long)b * gstride + c / cpg);
         const float v = x[b * in_bstride + i];
-        dst[(long long)b * C * P + i] = fmaxf((v - s[0]) * s[1] * gamma[c] + beta[c], 0.f);
+        dst[(long long)b * C * P + i] = fmaxf(convtile::gn_preact(v, s[0], s[1], gamma[c], beta[c]), 0.f);
     }
 }
 
 // weight preparation: the power-of-two scale of one matrix (max |w| * scale in [2^14, 2^15)) ...
 __global__ __launch_bounds__(256) void k_fpn_wscale(const float* __restrict__ w, long long n, float* __restrict__ sc) {
-    __shared__ float red[256];
     float m = 0.f;
     for (long long i = threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(w[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        int e = 0;
-        const float mx = red[0];
-        if (mx > 0.f && mx < INFINITY) frexpf(mx, &e);  // mx = f 2^e, f in [0.5, 1)
-        else e = 15;
-        sc[0] = ldexpf(1.f, 15 - e);
-        sc[1] = ldexpf(1.f, e - 15);
-    }
+    const float mx = convtile::block_absmax(m);
+    if (threadIdx.x == 0) convtile::pow2_scale(mx, sc);
 }
 
-// ... and the fragment images: [tap][ci / 16][co / 32][hi, lo][lane][8], lane l holding W[co = 32 cb + (l & 31)][ci = 16 ks + 8 (l >> 5) + j]
+// ... and the fragment images (vkn_convtile.h: frag_index)
 __global__ __launch_bounds__(256) void k_fpn_wsplit(const float* __restrict__ w, const float* __restrict__ sc, _Float16* __restrict__ img,
                                                     int Cout, int Cin, int taps) {
     const long long n = (long long)taps * Cin * Cout;  // one thread per (tap, ks, cb, lane, j)
@@ -287,18 +239,18 @@ __global__ __launch_bounds__(256) void k_fpn_wsplit(const float* __restrict__ w,
     const int co = cb * 32 + (lane & 31), ci = ks * 16 + (lane >> 5) * 8 + j;
     _Float16 h, l;
     vkn_split_f16(w[((long long)co * Cin + ci) * taps + tap] * sc[0], h, l);
-    const long long frag = (((long long)tap * nks + ks) * ncb + cb) * 2;
-    img[(frag * 64 + lane) * 8 + j] = h;
-    img[((frag + 1) * 64 + lane) * 8 + j] = l;
+    img[convtile::frag_index(tap, nks, ks, ncb, cb, 0, lane) * 8 + j] = h;
+    img[convtile::frag_index(tap, nks, ks, ncb, cb, 1, lane) * 8 + j] = l;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host side
 namespace {
 
-inline size_t fpn_align(size_t v) { return (v + 255) & ~(size_t)255; }
-inline int fpn_out(int n, int s) { return (n - 1) / s + 1; }  // 3x3 pad 1 and 1x1 pad 0: ceil(n / s)
+using convtile::align256;
+using convtile::conv_out;
+
 inline size_t fpn_part_bytes(int B, int Cout, int Ho, int Wo) {
-    return fpn_align((size_t)B * Cout * Ho * ((Wo + FPN_TILE - 1) / FPN_TILE) * 2 * sizeof(float));
+    return align256((size_t)B * Cout * Ho * convtile::runs(Wo) * 2 * sizeof(float));
 }
 
 struct FpnGn {  // a conv output's statistics for its consumers
@@ -325,22 +277,22 @@ FpnSrc fpn_src(const float* x, long long bstride, const FpnGn* gn) {
 // one conv (+ its GN statistics): a.src / nsrc / mode / pos / Cin / Hs / Ws / Hin / Win filled by the caller
 int fpn_conv(FpnConvArgs a, int ks, int stride, const void* wimg, int Cout, int B, float* out, long long out_bstride, float* st,
              int G, float* part, unsigned* status, hipStream_t stream) {
-    a.wscale = static_cast<const float*>(wimg);
-    a.wimg = reinterpret_cast<const _Float16*>(static_cast<const char*>(wimg) + FPN_IMG_HDR);
+    a.wscale = convtile::image_scale(wimg);
+    a.wimg = convtile::image_frags(wimg);
     a.Cout = Cout;
-    a.Ho = fpn_out(a.Hin, stride);
-    a.Wo = fpn_out(a.Win, stride);
-    a.ntx = (a.Wo + FPN_TILE - 1) / FPN_TILE;
+    a.Ho = conv_out(a.Hin, stride);
+    a.Wo = conv_out(a.Win, stride);
+    a.ntx = convtile::runs(a.Wo);
     a.out = out;
     a.out_bstride = out_bstride;
     a.part = part;
     a.status = status;
     const dim3 grid(a.ntx, a.Ho, B * ((Cout + 255) / 256));
-    const int xw = (FPN_TILE - 1) * stride + ks;
-    const size_t lds = (size_t)2 * ks * xw * FPN_PITCH * sizeof(_Float16);
-    if (ks == 3 && stride == 1) hipLaunchKernelGGL((k_fpn_conv<3, 1>), grid, dim3(FPN_THREADS), lds, stream, a);
-    else if (ks == 3 && stride == 2) hipLaunchKernelGGL((k_fpn_conv<3, 2>), grid, dim3(FPN_THREADS), lds, stream, a);
-    else if (ks == 1 && stride == 1) hipLaunchKernelGGL((k_fpn_conv<1, 1>), grid, dim3(FPN_THREADS), lds, stream, a);
+    const int xw = (convtile::TILE - 1) * stride + ks;
+    const size_t lds = (size_t)2 * ks * xw * convtile::PITCH * sizeof(_Float16);
+    if (ks == 3 && stride == 1) hipLaunchKernelGGL((k_fpn_conv<3, 1>), grid, dim3(convtile::THREADS), lds, stream, a);
+    else if (ks == 3 && stride == 2) hipLaunchKernelGGL((k_fpn_conv<3, 2>), grid, dim3(convtile::THREADS), lds, stream, a);
+    else if (ks == 1 && stride == 1) hipLaunchKernelGGL((k_fpn_conv<1, 1>), grid, dim3(convtile::THREADS), lds, stream, a);
     else return VKN_E_SHAPE;
     VKN_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_fpn_gn_finish, dim3(B * G), dim3(256), 0, stream, part, st, Cout, G, a.Ho, a.Wo, a.ntx, 1e-5f);
@@ -357,15 +309,13 @@ int fpn_apply(const float* x, long long in_bstride, const FpnGn& gn, float* dst,
     return VKN_OK;
 }
 
-bool fpn_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
 
 size_t vkn_conv_weight_bytes(int Cout, int Cin, int ksize) {
-    if (Cout <= 0 || Cin <= 0 || Cout % 32 || Cin % 32 || (ksize != 1 && ksize != 3)) return 0;
-    return FPN_IMG_HDR + (size_t)ksize * ksize * Cin * Cout * 2 * sizeof(_Float16);
+    if (!convtile::chan_chunks(Cout) || !convtile::chan_chunks(Cin) || !convtile::conv_ok(ksize, 1)) return 0;
+    return convtile::image_bytes(Cout, Cin, ksize * ksize);
 }
 
 int vkn_conv_prepare_f32(const float* w, int Cout, int Cin, int ksize, void* image, size_t image_bytes, void* stream) {
@@ -373,7 +323,7 @@ int vkn_conv_prepare_f32(const float* w, int Cout, int Cin, int ksize, void* ima
     const size_t need = vkn_conv_weight_bytes(Cout, Cin, ksize);
     if (!need) return VKN_E_SHAPE;
     if (image_bytes < need) return VKN_E_WORKSPACE;
-    if (!fpn_aligned(image)) return VKN_E_ALIGN;
+    if (!vkn_aligned(image, 16)) return VKN_E_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int taps = ksize * ksize;
     float* sc = static_cast<float*>(image);
@@ -381,7 +331,7 @@ int vkn_conv_prepare_f32(const float* w, int Cout, int Cin, int ksize, void* ima
     VKN_CHECK_LAUNCH();
     const long long n = (long long)taps * Cin * Cout;
     hipLaunchKernelGGL(k_fpn_wsplit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, sc,
-                       reinterpret_cast<_Float16*>(static_cast<char*>(image) + FPN_IMG_HDR), Cout, Cin, taps);
+                       const_cast<_Float16*>(convtile::image_frags(image)), Cout, Cin, taps);
     VKN_CHECK_LAUNCH();
     return VKN_OK;
 }
@@ -389,7 +339,7 @@ int vkn_conv_prepare_f32(const float* w, int Cout, int Cin, int ksize, void* ima
 size_t vkn_conv_gn_workspace_bytes(int B, int Cout, int H, int W, int stride, int upsample) {
     if (B <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return 0;
     const int Hin = upsample ? 2 * H : H, Win = upsample ? 2 * W : W;
-    return 256 + fpn_part_bytes(B, Cout, fpn_out(Hin, stride), fpn_out(Win, stride));
+    return 256 + fpn_part_bytes(B, Cout, conv_out(Hin, stride), conv_out(Win, stride));
 }
 
 int vkn_conv_gn_f32(const float* x, const float* pos, const float* in_stats, const float* in_gamma, const float* in_beta, int in_groups,
@@ -397,12 +347,11 @@ int vkn_conv_gn_f32(const float* x, const float* pos, const float* in_stats, con
                     int H, int W, int Cout, void* ws, size_t ws_bytes, void* stream) {
     if (!x || !wimg || !out || !out_stats) return VKN_E_ARG;
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return VKN_E_ARG;
-    if (Cin % 32 || Cout % 32 || Cin > 512 || Cout > 512 || (ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) ||
-        (ksize == 1 && stride != 1) || groups <= 0 || Cout % groups || (upsample && !in_stats) || (in_stats && pos) ||
-        (in_stats && (!in_gamma || !in_beta || in_groups <= 0 || Cin % in_groups)))
+    if (!convtile::chan_ok(Cin) || !convtile::chan_ok(Cout) || !convtile::conv_ok(ksize, stride) || groups <= 0 || Cout % groups ||
+        (upsample && !in_stats) || (in_stats && pos) || (in_stats && (!in_gamma || !in_beta || in_groups <= 0 || Cin % in_groups)))
         return VKN_E_SHAPE;
     if (!ws) return VKN_E_WORKSPACE;   // (include/vkn.h: a workspace that is NULL is VKN_E_WORKSPACE, as one that is too small)
-    if (!fpn_aligned(x) || !fpn_aligned(out) || !fpn_aligned(wimg) || !fpn_aligned(ws)) return VKN_E_ALIGN;
+    if (!vkn_aligned(x, 16) || !vkn_aligned(out, 16) || !vkn_aligned(wimg, 16) || !vkn_aligned(ws, 16)) return VKN_E_ALIGN;
     const size_t need = vkn_conv_gn_workspace_bytes(B, Cout, H, W, stride, upsample);
     if (ws_bytes < need) return VKN_E_WORKSPACE;
     const FpnGn gn{in_stats, in_gamma, in_beta, in_groups, in_groups > 0 ? Cin / in_groups : 1};
@@ -416,9 +365,21 @@ int vkn_conv_gn_f32(const float* x, const float* pos, const float* in_stats, con
     a.Ws = W;
     a.Hin = upsample ? 2 * H : H;
     a.Win = upsample ? 2 * W : W;
-    const long long P = (long long)fpn_out(a.Hin, stride) * fpn_out(a.Win, stride);
+    const long long P = (long long)conv_out(a.Hin, stride) * conv_out(a.Win, stride);
     return fpn_conv(a, ksize, stride, wimg, Cout, B, out, (long long)Cout * P, out_stats, groups,
                     reinterpret_cast<float*>(static_cast<char*>(ws) + 256), static_cast<unsigned*>(ws), static_cast<hipStream_t>(stream));
+}
+
+// the block's output from its raw output (include/vkn_fpn_train.h): the kernel that ends vkn_localization_fpn_f32
+int vkn_gn_relu_apply_f32(const float* r, const float* stats, const float* gamma, const float* beta, int groups, float* y, int B, int C,
+                          int H, int W, void* stream) {
+    if (!r || !stats || !gamma || !beta || !y) return VKN_E_ARG;
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return VKN_E_ARG;
+    if (!convtile::chan_ok(C) || groups <= 0 || C % groups || !convtile::fits_i32(B, C, H, W)) return VKN_E_SHAPE;
+    for (const void* p : {(const void*)r, (const void*)stats, (const void*)gamma, (const void*)beta, (const void*)y})
+        if (!vkn_aligned(p, 16)) return VKN_E_ALIGN;
+    const long long P = (long long)H * W;
+    return fpn_apply(r, C * P, FpnGn{stats, gamma, beta, groups, C / groups}, y, B, C, P, static_cast<hipStream_t>(stream));
 }
 
 // workspace carve of vkn_localization_fpn_f32: header | partials | stats[11] | raw maps
@@ -430,7 +391,7 @@ static size_t fpn_carve(int B, int C, int h, int w, int H4, int W4, int H5, int 
     size_t off = 256;
     auto take = [&](size_t bytes) {
         char* p = base ? base + off : nullptr;
-        off += fpn_align(bytes);
+        off += align256(bytes);
         return reinterpret_cast<float*>(p);
     };
     size_t part = fpn_part_bytes(B, 2 * C, h, w);
@@ -453,7 +414,7 @@ static size_t fpn_carve(int B, int C, int h, int w, int H4, int W4, int H5, int 
 static bool fpn_shapes_ok(int H2, int W2, int H3, int W3, int H4, int W4, int H5, int W5) {
     if (H2 <= 0 || W2 <= 0 || H3 <= 0 || W3 <= 0 || H4 <= 0 || W4 <= 0 || H5 <= 0 || W5 <= 0) return false;
     // every level reaches the stride-8 grid of P3: P2 by a stride-2 conv, P4 by one x2, P5 by two (:216-219 adds them)
-    return fpn_out(H2, 2) == H3 && fpn_out(W2, 2) == W3 && 2 * H4 == H3 && 2 * W4 == W3 && 4 * H5 == H3 && 4 * W5 == W3;
+    return conv_out(H2, 2) == H3 && conv_out(W2, 2) == W3 && 2 * H4 == H3 && 2 * W4 == W3 && 4 * H5 == H3 && 4 * W5 == W3;
 }
 
 size_t vkn_localization_fpn_workspace_bytes(int B, int C, int H2, int W2, int H3, int W3, int H4, int W4, int H5, int W5) {
@@ -468,14 +429,14 @@ int vkn_localization_fpn_f32(const float* p2, const float* p3, const float* p4, 
                              size_t ws_bytes, void* stream) {
     if (!p2 || !p3 || !p4 || !p5 || !wimg || !gamma || !beta || !loc || !sem) return VKN_E_ARG;
     if (B <= 0 || C <= 0) return VKN_E_ARG;
-    if (C % 32 || C > 256 || groups <= 0 || C % groups || !fpn_shapes_ok(H2, W2, H3, W3, H4, W4, H5, W5)) return VKN_E_SHAPE;
+    if (!convtile::chan_chunks(C) || C > 256 || groups <= 0 || C % groups || !fpn_shapes_ok(H2, W2, H3, W3, H4, W4, H5, W5)) return VKN_E_SHAPE;
     const bool with_ls = wimg[8] != nullptr;
     for (int i = 0; i < (with_ls ? 10 : 8); ++i)
-        if (!wimg[i] || !gamma[i] || !beta[i] || !fpn_aligned(wimg[i])) return VKN_E_ARG;
+        if (!wimg[i] || !gamma[i] || !beta[i] || !vkn_aligned(wimg[i], 16)) return VKN_E_ARG;
     if (with_ls != (wimg[9] != nullptr)) return VKN_E_ARG;
     if (!ws) return VKN_E_WORKSPACE;
     for (const void* p : {(const void*)p2, (const void*)p3, (const void*)p4, (const void*)p5, (const void*)loc, (const void*)sem, (const void*)ws})
-        if (!fpn_aligned(p)) return VKN_E_ALIGN;
+        if (!vkn_aligned(p, 16)) return VKN_E_ALIGN;
     FpnWs w;
     const size_t need = fpn_carve(B, C, H3, W3, H4, W4, H5, W5, static_cast<char*>(ws), &w);
     if (ws_bytes < need) return VKN_E_WORKSPACE;

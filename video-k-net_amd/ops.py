@@ -1438,6 +1438,11 @@ def lsap(cost):
 
 
 # ---------------------------------------------------------------------------------------------------------- localization FPN
+def _conv_out(n, stride):
+    """Output size of the block's convs (3x3 pad 1, 1x1 pad 0): ceil(n / stride)"""
+    return (n - 1) // stride + 1
+
+
 def conv_prepare(weight):
     """One conv weight [Cout, Cin, k, k] -> its prepared image (uint8 tensor of vkn_conv_weight_bytes): f16 hi / lo MFMA fragments,
     pre-scaled by a power of two (include/vkn.h: vkn_conv_prepare_f32).  Regenerate whenever the weight changes."""
@@ -1460,7 +1465,7 @@ def conv_gn(x, image, Cout, ksize, stride=1, groups=32, pos=None, in_stats=None,
     x = _req(x, 'x')
     B, Cin, H, W = x.shape
     Hin, Win = (2 * H, 2 * W) if upsample else (H, W)
-    Ho, Wo = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+    Ho, Wo = _conv_out(Hin, stride), _conv_out(Win, stride)
     dev = x.device
     out = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=dev)
     st = torch.empty((B, groups, 2), dtype=torch.float32, device=dev)
@@ -1551,7 +1556,7 @@ def conv_wgrad(dr, x, ksize, stride=1):
     dr, x = _req(dr, 'dr'), _req(x, 'x')
     B, Cin, H, W = x.shape
     Cout, dev = dr.shape[1], x.device
-    if tuple(dr.shape) != (B, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1):
+    if tuple(dr.shape) != (B, Cout, _conv_out(H, stride), _conv_out(W, stride)):
         raise ValueError(f'conv_wgrad: dr {tuple(dr.shape)} is not the output of x {tuple(x.shape)} at stride {stride}')
     L = _lib.lib()
     nb = L.vkn_conv_wgrad_workspace_bytes(B, Cin, H, W, Cout, int(ksize), int(stride))
@@ -1569,7 +1574,7 @@ def conv_dgrad(dr, image_t, Cin, H, W, ksize, stride=1):
     `conv_prepare(weight.flip(2, 3).transpose(0, 1))`: the flipped, channel-transposed weight as the forward engine's A operand."""
     dr = _req(dr, 'dr')
     B, Cout = dr.shape[:2]
-    if tuple(dr.shape[2:]) != ((H - 1) // stride + 1, (W - 1) // stride + 1):
+    if tuple(dr.shape[2:]) != (_conv_out(H, stride), _conv_out(W, stride)):
         raise ValueError(f'conv_dgrad: dr {tuple(dr.shape)} is not the output of a {H} x {W} input at stride {stride}')
     L = _lib.lib()
     nb = L.vkn_conv_dgrad_workspace_bytes(B, Cout, H, W, int(stride))
@@ -1585,7 +1590,7 @@ def conv_dgrad(dr, image_t, Cin, H, W, ksize, stride=1):
 
 
 def conv_gn_relu_fits(Cin, Cout, ksize, stride, groups):
-    """The envelope of the block's forward and backward kernels (include/vkn_fpn_train.h)"""
+    """The envelope of the block's forward and backward kernels (include/vkn_fpn_train.h; csrc/vkn_convtile.h: chan_ok, conv_ok)"""
     return (Cin % 32 == 0 and Cout % 32 == 0 and 0 < Cin <= 512 and 0 < Cout <= 512 and groups > 0 and Cout % groups == 0
             and (ksize, stride) in ((3, 1), (3, 2), (1, 1)))
 
