@@ -667,3 +667,123 @@ def init_case(B, C, Np, ncls, n_thing, H, W, seed, cat):
     sh = (B, -1, H, W)
     return (loc.view(B, C, H, W), sem.view(B, C, H, W), iw, sw, sb,
             dict(x_feats=xf.view(B, C, H, W), mask_preds=mp.view(sh), seg_preds=seg.view(sh), prop=prop))
+
+
+# ---- FPN backward: the two MFMA gradients of the conv alone, bit for bit (tests/test_gpu_fpn_bwd_pins.py).
+# k_conv_wgrad deals nruns = B Ho ceil(Wo / 64) pixel runs to nsplit workgroups per (32 ci, 128 co) tile; split sp walks the runs
+# nruns sp / nsplit .. nruns (sp + 1) / nsplit and accumulates them into the same tiles.  tests/fpn_bwd_ref.py's cases up to here give
+# every split ONE run.  These give a split several: across rows, across frames, full and ragged runs alternating, at stride 2 behind the
+# 64-pixel seam (ox0 = 64; dgrad: tx = 1 in both column parities), and more runs than VKN_FPN_WGRAD_MAX_SPLITS.
+# shape (B, Cin, Cout, H, W, k, s) -> what the split structure must be (runs, splits, {runs of a split: how many splits}); asserted by
+# tests/test_exact_premise.py against the split count READ BACK from the library's workspace size, not restated from the rule.
+FPN_BWD_PINS = {
+    (3, 512, 512, 3, 65, 3, 1): (18, 4, {4: 2, 5: 2}),            # two splits cross a frame boundary; full and one-pixel runs alternate
+    (3, 512, 512, 5, 131, 3, 2): (18, 4, {4: 2, 5: 2}),           # -> 3 x 66: every second run is the 2-pixel run behind the seam
+    (2, 512, 512, 3, 65, 1, 1): (12, 4, {3: 4}),                  # the 1x1 kernel
+    (3, 256, 256, 9, 65, 3, 1): (54, 16, {3: 10, 4: 6}),          # the shipped channel count
+    (1, 32, 32, 33, 65, 3, 1): (66, 64, {1: 62, 2: 2}),           # the MAX_SPLITS clamp; 33 rows in dgrad
+}
+FPN_BWD_LOW = ((2, 64, 96, 3, 65, 3, 1), (1, 96, 160, 5, 129, 3, 2))
+FPN_BWD_LOW_VARIANTS = ('wgrad-dr', 'wgrad-x', 'dgrad-dr', 'dgrad-w')      # kernel - the WIDE operand (the other is in {-1, 0, 1})
+FPN_BWD_WIDE = 8191                                               # 13 bits: two more than an f16 significand holds
+WGRAD_WS_FIXED = 1536                                             # status header, the two powers of two, the max |v| partials
+
+
+def fpn_bwd_id(shape, variant=None):
+    B, Ci, Co, H, W, k, s = shape
+    return f'{variant + "_" if variant else ""}B{B}_{Ci}to{Co}_{H}x{W}_k{k}s{s}'
+
+
+def wgrad_runs(shape):
+    """(nruns, runs per frame) of the weight gradient: 64-pixel runs of the output rows"""
+    B, _, _, H, W, _, s = shape
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    return B * Ho * ((Wo + 63) // 64), Ho * ((Wo + 63) // 64)
+
+
+def wgrad_nsplit_of(ws_bytes, shape):
+    """the number of partial tiles in a vkn_conv_wgrad_workspace_bytes answer (include/vkn_fpn_train.h: behind the fixed part the
+    workspace holds `splits` fp32 tiles [Cout][Cin k^2], a multiple of 256 bytes at any Cin, Cout of the envelope)"""
+    _, Ci, Co, _, _, k, _ = shape
+    tile = 4 * Co * Ci * k * k
+    assert ws_bytes > WGRAD_WS_FIXED and (ws_bytes - WGRAD_WS_FIXED) % tile == 0, (ws_bytes, shape)
+    return (ws_bytes - WGRAD_WS_FIXED) // tile
+
+
+def wgrad_split_runs(nruns, nsplit):
+    """[(first run, one past the last)] per split, k_conv_wgrad's own dealing"""
+    return [(nruns * sp // nsplit, nruns * (sp + 1) // nsplit) for sp in range(nsplit)]
+
+
+def conv_grads(x, w, dr, stride):
+    """(dw, dx) of F.conv2d(x, w, padding = k // 2) under the output gradient dr: autograd, in the operands' dtype"""
+    xx, ww = x.detach().clone().requires_grad_(), w.detach().clone().requires_grad_()
+    dx, dw = torch.autograd.grad(F.conv2d(xx, ww, None, stride, w.shape[-1] // 2), (xx, ww), dr)
+    return dw, dx
+
+
+def _conv_abs_sums(x, w, dr, stride):
+    """(sum |terms| of every dw element, of every dx element), float64: the same two gradients of the magnitudes"""
+    pad = w.shape[-1] // 2
+    return (torch.nn.grad.conv2d_weight(x.double().abs(), w.shape, dr.double().abs(), stride, pad),
+            torch.nn.grad.conv2d_input(x.shape, w.double().abs(), dr.double().abs(), stride, pad))
+
+
+def staged_pow2(t):
+    """the power of two under which the backward (and the weight image) stages a tensor: 2^(15 - e), max |v| = f 2^e, f in [0.5, 1)
+    (csrc/vkn_convtile.h: pow2_scale)"""
+    m = float(t.abs().max())
+    return 2.0 ** (15 - math.frexp(m)[1]) if m > 0 else 1.0
+
+
+def conv_bwd_case(shape, seed, span=3):
+    """x, w, dr integers in [-span, span] -> dict(x, w, dr, dw, dx): dw, dx float64 autograd of F.conv2d.  The power of two per tensor
+    is exact on them and leaves every low half empty (asserted).  Premise on sum |terms| of dw and of dx, non-vacuity."""
+    B, Ci, Co, H, W, k, s = shape
+    g = gen(seed)
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    x, w, dr = ints((B, Ci, H, W), -span, span, g), ints((Co, Ci, k, k), -span, span, g), ints((B, Co, Ho, Wo), -span, span, g)
+    name = 'conv_bwd ' + fpn_bwd_id(shape)
+    for t in (x, w, dr):
+        if bool((split_f16(t * staged_pow2(t))[1] != 0).any()):
+            raise PremiseError(name + ': a staged operand has a non-empty low half')
+    premise(name, *_conv_abs_sums(x, w, dr, s))
+    dw, dx = conv_grads(x.double(), w.double(), dr.double(), s)
+    non_vacuous(name, dw, dx)
+    return dict(x=x, w=w, dr=dr, dw=dw, dx=dx)
+
+
+def conv_bwd_low_case(shape, variant, seed, wide=FPN_BWD_WIDE):
+    """One of FPN_BWD_LOW_VARIANTS: the WIDE operand holds integers in [-wide, wide], its partner in the product integers in {-1, 0, 1};
+    the third operand (x for dgrad, w for wgrad) is not read by the kernel under test.  The MFMA kernels drop lo * lo: with an empty low
+    half on one side hi * hi + hi * lo + lo * hi is the whole product.  Asserted here, from the operands: hi + lo reproduces every staged
+    value of the wide operand (v 2^(15 - e)), at least FPN_LOW_SHARE of them have lo != 0, the partner's low halves are empty, and
+    max sum (|hi| + |lo|) |partner| < 2^24 in units of the wide operand's finest bit.  -> dict(x, w, dr, out float64, low_share)"""
+    B, Ci, Co, H, W, k, s = shape
+    kernel, which = variant.split('-')
+    g = gen(seed)
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    shapes = dict(x=(B, Ci, H, W), w=(Co, Ci, k, k), dr=(B, Co, Ho, Wo))
+    partner = {'wgrad': {'dr': 'x', 'x': 'dr'}, 'dgrad': {'dr': 'w', 'w': 'dr'}}[kernel][which]
+    t = {n: ints(sh, -wide, wide, g) if n == which else ints(sh, -1, 1, g) for n, sh in shapes.items()}
+    name = 'conv_bwd_low ' + fpn_bwd_id(shape, variant)
+    sc = staged_pow2(t[which])
+    staged = t[which].double() * sc
+    hi, lo = split_f16(staged)
+    if not torch.equal(hi.double() + lo.double(), staged):
+        raise PremiseError(name + ': a staged value does not split exactly into f16 hi + lo')
+    halves = (hi.double().abs() + lo.double().abs()) / sc               # the accumulator sees hi p and lo p as separate terms
+    if not bool((halves == halves.round()).all()):
+        raise PremiseError(name + ': a half is no multiple of the operand\'s finest bit')
+    if bool((split_f16(t[partner] * staged_pow2(t[partner]))[1] != 0).any()):
+        raise PremiseError(name + ': the narrow operand has a non-empty low half')
+    low_share = float((lo != 0).double().mean())
+    if low_share < FPN_LOW_SHARE:
+        raise PremiseError(f'{name}: only {low_share:.3f} of the staged values have a non-zero low half (< {FPN_LOW_SHARE})')
+    mags = {n: (halves if n == which else v.double().abs()) for n, v in t.items()}
+    dw_abs, dx_abs = _conv_abs_sums(mags['x'], mags['w'], mags['dr'], s)
+    dw, dx = conv_grads(t['x'].double(), t['w'].double(), t['dr'].double(), s)
+    out, out_abs = (dw, dw_abs) if kernel == 'wgrad' else (dx, dx_abs)
+    premise(name, out_abs)
+    non_vacuous(name, out)
+    return dict(x=t['x'], w=t['w'], dr=t['dr'], out=out, low_share=low_share)

@@ -38,6 +38,15 @@ BLOCK_CASES = {
     'k3s1-288to160-3x7-g32': (2, 288, 160, 3, 7, 3, 1, 32),       # past 256 input and 128 output channels: a second workgroup column in both gradients
     'k3s2-160to288-5x9-g32': (2, 160, 288, 5, 9, 3, 2, 32),       # ... the other way round, at stride 2; all four waves of the input gradient
     'k1s1-256to256-2x3-g32': (1, 256, 256, 2, 3, 1, 1, 32),       # the shipped channel count
+    'k3s1-32to32-33x65-g8-B1': (1, 32, 32, 33, 65, 3, 1, 8),      # 66 runs: more than VKN_FPN_WGRAD_MAX_SPLITS, two splits sum two runs; 33 rows
+    'k3s2-32to32-9x131-g8': (2, 32, 32, 9, 131, 3, 2, 8),         # -> 5 x 66: the 64-pixel seam at stride 2 through GroupNorm, wgrad and dgrad
+}
+# name: (B, Cin, Cout, H, W, k, stride): the convolution's two gradients alone where a split of the weight gradient sums 4 or 5 runs
+# (tests/exact_cases.py: FPN_BWD_PINS pins the same shapes bit for bit on integers).  No GroupNorm, no ReLU edge: no seed search.  Kept
+# out of BLOCK_CASES: 512 -> 512 channels have no seed clear of the ReLU edge, and tools/convtile_ab.py hashes BLOCK_CASES only.
+CONV_CASES = {
+    'k3s1-512to512-3x65-B3': (3, 512, 512, 3, 65, 3, 1),          # 18 runs in 4 splits of 4, 5, 4, 5; full and one-pixel runs alternate
+    'k3s2-512to512-5x131-B3': (3, 512, 512, 5, 131, 3, 2),        # -> 3 x 66: every second run is the 2-pixel run behind the seam
 }
 # name: (B, C, H, W, groups)
 GN_CASES = {
@@ -168,6 +177,21 @@ def block_case(name):
         out[key] = dict(y=y.detach(), dr=dr, dx=dx, dw=dw, dgamma=dg, dbeta=db, r=r.detach())
         leaves, r, _ = _compose(x, w, gamma, beta, G, s, dt)
         out[key]['conv_dx'], out[key]['conv_dw'] = torch.autograd.grad(r, leaves[:2], dy.to(dt))       # the convolution alone, dy as the gradient of r
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def conv_case(name):
+    """Gaussian operands as `_block_operands` draws them (seed SEEDS[0]), the float64 autograd of F.conv2d and torch's fp32 one: keys
+    `conv_dw`, `conv_dx`, judged by `bound` like the block cases'"""
+    shape = CONV_CASES[name]
+    s = shape[6]
+    x, w, _, _, dy = _block_operands(shape + (32,), SEEDS[0])
+    out = dict(x=x, w=w, dy=dy, stride=s, k=shape[5], seed=SEEDS[0])
+    for key, dt in (('ref', torch.float64), ('f32', torch.float32)):
+        xx, ww = (t.detach().to(dt).clone().requires_grad_() for t in (x, w))
+        dx, dw = torch.autograd.grad(F.conv2d(xx, ww, None, s, shape[5] // 2), (xx, ww), dy.to(dt))
+        out[key] = dict(conv_dx=dx, conv_dw=dw)
     return out
 
 

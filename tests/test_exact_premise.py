@@ -213,3 +213,87 @@ def test_conv_unequal_channels_and_probes_fp32_equal_integer_reference():
             assert n >= 1 and int((x != 0).sum()) + (int((pos != 0).sum()) if pos is not None else 0) == n      # one pixel per probe
     assert (0, 63) in ec.probe_pixels(3, 65, 1) and (0, 64) in ec.probe_pixels(3, 65, 1) and (2, 0) in ec.probe_pixels(3, 65, 1)
     assert (4, 126) in ec.probe_pixels(5, 129, 2) and (4, 128) in ec.probe_pixels(5, 129, 2)                   # output columns 63 and 64
+
+
+# ---- the FPN backward's two MFMA gradients bit for bit (tests/test_gpu_fpn_bwd_pins.py)
+def _wgrad_nsplit(vkn, shape):
+    """the split count of a shape as the LIBRARY carves it (a host function: no device), checked against the header's constants"""
+    B, Ci, Co, H, W, k, s = shape
+    nb = vkn._lib.lib().vkn_conv_wgrad_workspace_bytes(B, Ci, H, W, Co, k, s)
+    nsplit = ec.wgrad_nsplit_of(nb, shape)
+    K = vkn._lib.FPN_TRAIN
+    nruns, _ = ec.wgrad_runs(shape)
+    tiles = (Ci // 32) * ((Co + 127) // 128)
+    assert nsplit == min(max(1, K['VKN_FPN_WGRAD_TARGET_WGS'] // tiles), K['VKN_FPN_WGRAD_MAX_SPLITS'], nruns), (shape, nsplit)
+    return nsplit
+
+
+def test_fpn_bwd_pins_walk_several_runs_per_split(vkn):
+    """The reason these cases exist: a split of the weight gradient that sums MORE THAN ONE pixel run.  From the split count read back
+    from the library: the structure each case names, some split with >= 3 runs, some split across a frame boundary, runs not divisible
+    by the splits, the VKN_FPN_WGRAD_MAX_SPLITS clamp at work, a stride-2 case behind the 64-pixel seam, more than 5 image rows."""
+    most, crossing, uneven, clamped = 0, 0, 0, 0
+    for shape, (want_runs, want_splits, want_sizes) in ec.FPN_BWD_PINS.items():
+        nruns, per_frame = ec.wgrad_runs(shape)
+        nsplit = _wgrad_nsplit(vkn, shape)
+        spans = ec.wgrad_split_runs(nruns, nsplit)
+        sizes = {}
+        for a, b in spans:
+            sizes[b - a] = sizes.get(b - a, 0) + 1
+        assert (nruns, nsplit, sizes) == (want_runs, want_splits, want_sizes), \
+            f'{shape}: {nruns} runs in {nsplit} splits of {sizes} runs — the split rule changed: this case no longer pins what exact_cases.FPN_BWD_PINS says'
+        assert spans[0][0] == 0 and spans[-1][1] == nruns and all(p[1] == q[0] for p, q in zip(spans, spans[1:]))
+        most = max(most, max(sizes))
+        crossing += sum(1 for a, b in spans if b > a and a // per_frame != (b - 1) // per_frame)
+        uneven += nruns % nsplit != 0
+        clamped += nsplit == vkn._lib.FPN_TRAIN['VKN_FPN_WGRAD_MAX_SPLITS'] < nruns
+    assert most >= 3, f'every split of every case owns at most {most} runs: the run loop of k_conv_wgrad is pinned nowhere'
+    assert crossing >= 2 and uneven >= 1 and clamped >= 1, (crossing, uneven, clamped)
+    s2 = [sh for sh in ec.FPN_BWD_PINS if sh[6] == 2]
+    assert any((sh[4] - 1) // 2 + 1 > 64 and ((sh[4] - 1) // 2 + 1) % 64 for sh in s2)          # a ragged run behind the seam, odd W: both parities differ
+    assert max(sh[3] for sh in ec.FPN_BWD_PINS) > 5 and {(sh[5], sh[6]) for sh in ec.FPN_BWD_PINS} == set(ec.FPN_KS)
+    # ... and the cases of tests/fpn_bwd_ref.py before these: one run per split, all of them (what the pins add)
+    import fpn_bwd_ref as R
+    old = [c[:7] for n, c in R.BLOCK_CASES.items() if n not in ('k3s1-32to32-33x65-g8-B1', 'k3s2-32to32-9x131-g8')]
+    assert all(ec.wgrad_runs(sh)[0] <= _wgrad_nsplit(vkn, sh) for sh in old)
+    assert [c[:7] for c in R.CONV_CASES.values()] == list(ec.FPN_BWD_PINS)[:2]
+
+
+@pytest.mark.parametrize('i', range(len(ec.FPN_BWD_PINS)), ids=[ec.fpn_bwd_id(s) for s in ec.FPN_BWD_PINS])
+def test_fpn_bwd_pins_fp32_equal_float64_reference(i):
+    """`conv_bwd_case` asserts premise, non-vacuity and empty low halves; torch's CPU fp32 autograd — another summation order than the
+    kernels' — equals the float64 reference bit for bit"""
+    shape = list(ec.FPN_BWD_PINS)[i]
+    d = ec.conv_bwd_case(shape, 3800 + i)
+    dw, dx = ec.conv_grads(d['x'], d['w'], d['dr'], shape[6])
+    assert _same(dw, d['dw']) and _same(dx, d['dx']), shape
+    assert all(float(d[k].abs().max()) <= 3.0 and torch.equal(d[k], d[k].round()) for k in ('x', 'w', 'dr'))
+
+
+@pytest.mark.parametrize('variant', ec.FPN_BWD_LOW_VARIANTS)
+def test_fpn_bwd_low_halves_stay_exact(variant):
+    """`conv_bwd_low_case` asserts the exact split of the staged wide operand, its low-half share, the partner's empty low halves and
+    the premise on the halves; here the staged scale is the kernel's (max |v| 2^(15 - e) in [2^14, 2^15)), the wide operand really is
+    wider than an f16 significand, and fp32 autograd equals float64"""
+    kernel, which = variant.split('-')
+    for j, shape in enumerate(ec.FPN_BWD_LOW):
+        d = ec.conv_bwd_low_case(shape, variant, 3900 + 4 * j + ec.FPN_BWD_LOW_VARIANTS.index(variant))
+        wide = d[which]
+        assert 2.0 ** 14 <= float(wide.abs().max()) * ec.staged_pow2(wide) < 2.0 ** 15 and 4095 < float(wide.abs().max()) <= ec.FPN_BWD_WIDE
+        assert d['low_share'] >= ec.FPN_LOW_SHARE
+        narrow = [k for k in ('x', 'w', 'dr') if k != which]
+        assert all(set(d[k].unique().tolist()) == {-1.0, 0.0, 1.0} for k in narrow)
+        dw, dx = ec.conv_grads(d['x'], d['w'], d['dr'], shape[6])
+        assert _same(dw if kernel == 'wgrad' else dx, d['out']), (shape, variant)
+
+
+def test_a_fpn_bwd_case_outside_its_premise_fails_as_a_test_bug():
+    with pytest.raises(ec.PremiseError, match='fp32 accumulation is not exact'):       # |v| <= 200 at 512 channels: dx sums of about 2^25
+        ec.conv_bwd_case((3, 512, 512, 3, 65, 3, 1), 3800, span=200)
+    with pytest.raises(ec.PremiseError, match='non-empty low half'):                   # 13-bit integers as a "plain" operand
+        ec.conv_bwd_case((1, 32, 32, 1, 1, 1, 1), 3800, span=8191)
+    with pytest.raises(ec.PremiseError, match='fp32 accumulation is not exact'):       # the low-half recipe at 512 channels, 15-bit integers
+        ec.conv_bwd_low_case((3, 512, 512, 3, 65, 3, 1), 'dgrad-dr', 3900, wide=32767)
+    with pytest.raises(ec.PremiseError, match='low half'):                             # 11 bits: nothing reaches the low half
+        ec.conv_bwd_low_case(ec.FPN_BWD_LOW[0], 'wgrad-x', 3900, wide=2047)
+    assert ec.staged_pow2(torch.tensor([3.0, -1.0])) == 2.0 ** 13 and ec.staged_pow2(torch.tensor([8191.0])) == 4.0 and ec.staged_pow2(torch.zeros(2)) == 1.0

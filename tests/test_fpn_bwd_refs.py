@@ -1,12 +1,16 @@
 """CPU: the premises of tests/test_gpu_fpn_bwd.py, asserted on the operands it will use (tests/fpn_bwd_ref.py), and the Python surface
 of the block that needs no device: the `fused_backward` keyword and the envelope predicate."""
 import inspect
+import os
+import re
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 import fpn_bwd_ref as R
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'vkn_fpn_train.h')
 
 
 @pytest.mark.parametrize('name', list(R.GN_CASES))
@@ -61,6 +65,11 @@ def test_the_cases_cover_the_kernel_paths():
     runs = lambda c: c[0] * ((c[3] - 1) // c[6] + 1) * (((c[4] - 1) // c[6] + 1 + 63) // 64)              # noqa: E731
     assert min(runs(c) for c in cases) == 1 and any(((c[4] - 1) // c[6] + 1) % 64 == 1 for c in cases) and any(c[4] == 64 and c[6] == 1 for c in cases)
     assert any(co // g == 1 for _, _, co, *_, g in cases) and any(g == 32 and co == 64 for _, _, co, *_, g in cases)
+    wo = lambda c: (c[4] - 1) // c[6] + 1                                                                 # noqa: E731
+    assert any(c[6] == 2 and wo(c) > 64 for c in cases), 'no stride-2 case crosses the 64-pixel run seam (wgrad ox0 = 64, dgrad tx = 1)'
+    max_splits = int(re.search(r'#define\s+VKN_FPN_WGRAD_MAX_SPLITS\s+(\d+)', open(HEADER).read()).group(1))
+    assert any(runs(c) > max_splits for c in cases), 'no case has more runs than VKN_FPN_WGRAD_MAX_SPLITS: every split sums one run'
+    assert max(c[3] for c in cases) > 5                                                                   # the dgrad grid's y dimension is H
     assert any(H * W > 2048 for _, _, H, W, _ in R.GN_CASES.values())                                     # two runs of the GroupNorm backward's sums
     assert R.DY_SCALES == (1.0, 2.0 ** -20, 2.0 ** 10)
 
@@ -109,3 +118,19 @@ def test_module_case_clears_the_margin_in_every_layer(vkn):
     assert len(c['ref']) == 2 + 4 + 3 * 9 and set(c['ref']) == set(c['f32'])
     for k in c['ref']:
         assert float(c['ref'][k].abs().max()) > 0 and 0 < R.bound(c['f32'][k], c['ref'][k])[0] < 1e-3 * float(c['ref'][k].abs().max()), k
+
+
+@pytest.mark.parametrize('name', list(R.CONV_CASES))
+def test_conv_cases_have_positive_bounds_and_stay_out_of_the_block_cases(name):
+    """the multi-run conv-only cases: Gaussian operands of SEEDS[0], every bound positive and below 1e-3 of its tensor; they are the
+    first two shapes of exact_cases.FPN_BWD_PINS and no entry of BLOCK_CASES"""
+    import exact_cases as ec
+    c = R.conv_case(name)
+    shape = R.CONV_CASES[name]
+    B, Cin, Cout, H, W, k, s = shape
+    assert shape == list(ec.FPN_BWD_PINS)[list(R.CONV_CASES).index(name)] and name not in R.BLOCK_CASES
+    assert all(shape != b[:7] for b in R.BLOCK_CASES.values())
+    assert c['seed'] == R.SEEDS[0] and tuple(c['ref']['conv_dw'].shape) == (Cout, Cin, k, k) and tuple(c['ref']['conv_dx'].shape) == (B, Cin, H, W)
+    for key in ('conv_dw', 'conv_dx'):
+        b, e32 = R.bound(c['f32'][key], c['ref'][key])
+        assert 0 < b < 1e-3 * float(c['ref'][key].abs().max()), (key, b)

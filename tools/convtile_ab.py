@@ -7,6 +7,9 @@ another build (the headers must be the same).  Hashed, all on seeded operands:
   * vkn_localization_fpn_f32 with and without the loc / seg convs at B = 2, C = 64, levels (7, 135), (4, 68), (2, 34), (1, 17): two runs
     per row at the stride-8 grid, a partial run at every level.
 The first line, behind a `#`, names the device and the library that was loaded; compare the rest (profiles/convtile_ab.txt).
+BLOCK_CASES has since gained 'k3s1-32to32-33x65-g8-B1' and 'k3s2-32to32-9x131-g8': the tool now emits 8 tensors x 3 scales more for
+them than profiles/convtile_ab.txt holds, which was not regenerated (its 501 lines are the A/B of the engine's move, at the cases of then).
+The conv-only CONV_CASES of tests/fpn_bwd_ref.py are not hashed.
 
     python tools/convtile_ab.py [--lib PATH/libvkn.so] [--out FILE]
 """
