@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libvkn.so')
-SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_segloss.hip', 'vkn_stq.hip', 'vkn_vpq.hip', 'vkn_fpn_bwd.hip', 'vkn_api.hip')
+SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_segloss.hip', 'vkn_stq.hip', 'vkn_vpq.hip', 'vkn_fpn_bwd.hip', 'vkn_msda.hip', 'vkn_api.hip')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 # The C ABI, one header per part, each behind the headers it #includes.  A new part is one more name here.
 ABI_HEADERS = ('vkn.h', 'vkn_track.h', 'vkn_track_train.h', 'vkn_gt.h', 'vkn_decode.h')
@@ -29,6 +29,8 @@ METRIC_HEADERS = ('vkn_stq.h',)
 WINDOW_METRIC_HEADERS = ('vkn_vpq.h',)
 # Training parts: a fifth such table `ABI_TRAIN` behind the four, on the same terms; its constants in their own record `FPN_TRAIN`.
 TRAIN_HEADERS = ('vkn_fpn_train.h',)
+# Neck parts: a sixth such table `ABI_NECK` behind the five, on the same terms; its constants in their own record `MSDA`.
+NECK_HEADERS = ('vkn_msda.h',)
 
 
 class VknLibraryError(RuntimeError):
@@ -133,22 +135,24 @@ def read_abi(include_dir, names):
 
 
 def _each(field, tables=None):
-    """[(header, name, value)] of one field of every header's record — `ABI`'s, then `ABI_EXT`'s, `ABI_METRIC`'s, `ABI_WINDOW_METRIC`'s, `ABI_TRAIN`'s — in the headers' order"""
-    return [(h, k, v) for t in (tables or (ABI, ABI_EXT, ABI_METRIC, ABI_WINDOW_METRIC, ABI_TRAIN)) for h, hdr in t.items() for k, v in getattr(hdr, field).items()]
+    """[(header, name, value)] of one field of every header's record — `ABI`'s, then `ABI_EXT`'s, `ABI_METRIC`'s, `ABI_WINDOW_METRIC`'s, `ABI_TRAIN`'s, `ABI_NECK`'s — in the headers' order"""
+    return [(h, k, v) for t in (tables or (ABI, ABI_EXT, ABI_METRIC, ABI_WINDOW_METRIC, ABI_TRAIN, ABI_NECK)) for h, hdr in t.items() for k, v in getattr(hdr, field).items()]
 
 
-_ALL = read_abi(INCLUDE, ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS + TRAIN_HEADERS)          # ONE reading: includes resolve, a name declared twice is an error
+_ALL = read_abi(INCLUDE, ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS + TRAIN_HEADERS + NECK_HEADERS)          # ONE reading: includes resolve, a name declared twice is an error
 ABI = {h: _ALL[h] for h in ABI_HEADERS}
 ABI_EXT = {h: _ALL[h] for h in EXTENSION_HEADERS}
 ABI_METRIC = {h: _ALL[h] for h in METRIC_HEADERS}
 ABI_WINDOW_METRIC = {h: _ALL[h] for h in WINDOW_METRIC_HEADERS}
 ABI_TRAIN = {h: _ALL[h] for h in TRAIN_HEADERS}
+ABI_NECK = {h: _ALL[h] for h in NECK_HEADERS}
 HEADER, PROTOS, SYMBOLS, STRUCTS, MIRRORS = (getattr(ABI['vkn.h'], k) for k in ('path', 'protos', 'symbols', 'structs', 'mirrors'))
 CONSTS = {k: v for _, k, v in _each('consts', (ABI,))}      # every ABI header's constants: no name is declared twice
 SEG = ABI_EXT['vkn_seg_loss.h'].consts              # an extension's constants stay in its own record
 STQ = ABI_METRIC['vkn_stq.h'].consts                # ... and so do a metric part's
 VPQ = ABI_WINDOW_METRIC['vkn_vpq.h'].consts         # ... and a windowed metric part's
 FPN_TRAIN = ABI_TRAIN['vkn_fpn_train.h'].consts     # ... and a training part's
+MSDA = ABI_NECK['vkn_msda.h'].consts                # ... and a neck part's
 GT_MAX_IMAGES = CONSTS['VKN_GT_MAX_IMAGES']
 GT_MAX_CLASSES = CONSTS['VKN_GT_MAX_CLASSES']
 GT_MAX_IDS = CONSTS['VKN_GT_MAX_IDS']
@@ -191,9 +195,10 @@ POINTER_EXCEPTIONS = {
     ('vkn_qd_tracker_state_layout', 'offsets12'): ctypes.POINTER(ctypes.c_size_t),  # a HOST array the call fills, (c_size_t * 12)()
     ('vkn_stq_state_layout', 'offsets8'): ctypes.POINTER(ctypes.c_size_t),          # likewise, (c_size_t * 8)()
     ('vkn_vpq_state_layout', 'offsets4'): ctypes.POINTER(ctypes.c_size_t),          # likewise, (c_size_t * 4)()
+    ('vkn_msda_sample_f32', 'shapes'): ctypes.POINTER(ctypes.c_int),                # a HOST array of L (H, W) pairs, (c_int * 2L)(...)
 }
 for _fn, _p in set(POINTER_EXCEPTIONS) - {(fn, q[0]) for _, fn, (_, params) in _each('protos') for q in params}:
-    raise VknLibraryError(f'POINTER_EXCEPTIONS names {_fn}({_p}), which none of the headers {ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS + TRAIN_HEADERS} declares')
+    raise VknLibraryError(f'POINTER_EXCEPTIONS names {_fn}({_p}), which none of the headers {ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS + TRAIN_HEADERS + NECK_HEADERS} declares')
 
 DEBUG_LIBPATH = os.path.join(LIBDIR, 'libvkn_debug.so')
 

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from . import autograd as vag
 from . import ops
 from .losses import accuracy, reduce_mean
-from .registry import HAVE_MM, HEADS, build_assigner, build_loss, build_sampler, register_head
+from .registry import HAVE_MM, HEADS, NECKS, build_assigner, build_loss, build_sampler, register_head
 from .semantic_fpn import SemanticFPNWrapper
 
 
@@ -114,8 +114,11 @@ class ConvKernelHead(nn.Module):
             return build_neck(cfg)
         if cfg.get('type') in HEADS:
             return HEADS.build(cfg)
-        raise NotImplementedError(f'localization_fpn type {cfg.get("type")!r} is not registered (the FPN neck is backbone-side, '
-                                  'outside this package: pass an nn.Module or register one in video_k_net_amd.HEADS)')
+        if cfg.get('type') in NECKS:
+            return NECKS.build(cfg)
+        raise NotImplementedError(f'localization_fpn type {cfg.get("type")!r} is not registered (this package builds '
+                                  'SemanticFPNWrapper and MSDeformAttnPixelDecoder: pass an nn.Module or register a neck in '
+                                  'video_k_net_amd.NECKS)')
 
     def _init_layers(self):
         """knet/det/kernel_head.py:122-168 — same attribute names, creation order and shapes."""

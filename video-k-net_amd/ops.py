@@ -1595,6 +1595,66 @@ def conv_gn_relu_fits(Cin, Cout, ksize, stride, groups):
             and (ksize, stride) in ((3, 1), (3, 2), (1, 1)))
 
 
+# ------------------------------------------------------------------------------------------- deformable-attention neck
+_MSDA = _lib.MSDA
+
+
+def msda_fits(M, D, L, P):
+    """The envelope of the sampling core (include/vkn_msda.h), sizes aside"""
+    return (D in (16, 32, 64) and M > 0 and (M * D) % 32 == 0 and M * D <= _MSDA['VKN_MSDA_MAX_CHANNELS']
+            and 1 <= L <= _MSDA['VKN_MSDA_MAX_LEVELS'] and 1 <= P <= _MSDA['VKN_MSDA_MAX_POINTS'])
+
+
+def _req_rows(t, name, width):
+    """A [rows, >= width] fp32 view whose rows may be strided (a column range of a GEMM output): (tensor, row stride in floats)"""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.VknLibraryError(f'{name}: expected a CUDA/HIP tensor — the MI355X path has no CPU fallback')
+    if t.dtype != torch.float32:
+        raise TypeError(f'{name}: expected float32, got {t.dtype}')
+    if t.dim() != 2 or t.shape[1] != width:
+        raise ValueError(f'{name}: expected [rows, {width}], got {tuple(t.shape)}')
+    if t.stride(1) != 1 or t.stride(0) < width:
+        t = t.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t, t.stride(0)
+
+
+def msda_sample(value, spatial_shapes, offsets, logits, ref, num_heads, num_points):
+    """The sampling core of multi-scale deformable attention (include/vkn_msda.h: vkn_msda_sample_f32).  value [B, S, M D] with the
+    levels of `spatial_shapes` = [(H_l, W_l)] concatenated; offsets [B Q, 2 M L P] and logits [B Q, M L P], the raw outputs of the
+    `sampling_offsets` / `attention_weights` Linears (column ranges of one GEMM output are taken as they are, by row stride);
+    ref [Q, L, 2] normalised (x, y).  -> [B, Q, M D]."""
+    value, ref = _req(value, 'value'), _req(ref, 'ref')
+    B, S, C = value.shape
+    M, P, L = int(num_heads), int(num_points), len(spatial_shapes)
+    Q = ref.shape[0]
+    if C % M or tuple(ref.shape) != (Q, L, 2) or sum(int(h) * int(w) for h, w in spatial_shapes) != S:
+        raise ValueError(f'msda_sample: value {tuple(value.shape)}, ref {tuple(ref.shape)}, levels {list(spatial_shapes)}, {M} heads do not fit')
+    offsets, ld_off = _req_rows(offsets, 'offsets', 2 * M * L * P)
+    logits, ld_logits = _req_rows(logits, 'logits', M * L * P)
+    if offsets.shape[0] != B * Q or logits.shape[0] != B * Q:
+        raise ValueError(f'msda_sample: {offsets.shape[0]} offset rows, {logits.shape[0]} logit rows for B Q = {B * Q}')
+    out = torch.empty((B, Q, C), dtype=torch.float32, device=value.device)
+    shapes = (ctypes.c_int * (2 * L))(*[int(v) for hw in spatial_shapes for v in hw])
+    with torch.cuda.device(value.device):
+        check(_lib.lib().vkn_msda_sample_f32(_ptr(value), _ptr(offsets), ld_off, _ptr(logits), ld_logits, _ptr(ref), shapes, _ptr(out),
+                                             B, Q, M, C // M, L, P, _stream()))
+    return out
+
+
+def layernorm_act(x, gamma, beta, resid=None, eps=1e-5, act=0):
+    """act(LayerNorm(x + resid) gamma + beta) per row of [rows, C <= 256] (include/vkn.h: vkn_layernorm_act_fwd_f32), no gradient"""
+    x = _req(x, 'x')
+    M, C = x.shape
+    resid = _req(resid, 'resid') if resid is not None else None
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        check(_lib.lib().vkn_layernorm_act_fwd_f32(_ptr(x), C, _ptr(resid), C, _ptr(_req(gamma, 'gamma')), _ptr(_req(beta, 'beta')),
+                                                   float(eps), int(act), _ptr(out), C, None, M, C, _stream()))
+    return out
+
+
 def _four_maps(who, state, gt_sem, gt_ins, pred_sem, pred_ins):
     """(maps, B, HW) of a map meter's update: four int32 tensors [H,W] or [B,H,W] of one shape on the state's device."""
     maps = [_req_plain(m, name, torch.int32) for m, name in zip((gt_sem, gt_ins, pred_sem, pred_ins), ('gt_sem', 'gt_ins', 'pred_sem', 'pred_ins'))]

@@ -49,13 +49,14 @@ class Registry:
 
 try:  # real mmdet / mmcv present: be a plug-in of the reference's own registries
     from mmcv.cnn.bricks.transformer import TRANSFORMER_LAYER, build_transformer_layer  # type: ignore
-    from mmdet.models.builder import HEADS, build_head, build_loss  # type: ignore
+    from mmdet.models.builder import HEADS, NECKS, build_head, build_loss, build_neck  # type: ignore
     from mmdet.models.roi_heads import BaseRoIHead  # type: ignore
     from mmdet.core import build_assigner, build_sampler  # type: ignore
     HAVE_MM = True
 except Exception:  # noqa: BLE001  (mmcv/mmdet are not installed in the build image)
     HAVE_MM = False
     HEADS = Registry('models')
+    NECKS = Registry('neck')
     TRANSFORMER_LAYER = Registry('transformerLayer')
     LOSSES = Registry('loss')
     BBOX_ASSIGNERS = Registry('bbox_assigner')
@@ -70,6 +71,9 @@ except Exception:  # noqa: BLE001  (mmcv/mmdet are not installed in the build im
 
     def build_head(cfg):
         return HEADS.build(cfg)
+
+    def build_neck(cfg):
+        return NECKS.build(cfg)
 
     def build_transformer_layer(cfg, default_args=None):
         return TRANSFORMER_LAYER.build(cfg, default_args)
@@ -128,6 +132,10 @@ def _register_training_components():
 
 def register_head(cls):
     return HEADS.register_module(force=True)(cls)
+
+
+def register_neck(cls):
+    return NECKS.register_module(force=True)(cls)
 
 
 def register_transformer_layer(cls):
