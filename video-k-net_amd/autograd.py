@@ -452,3 +452,35 @@ class ConvGNReLUFn(torch.autograd.Function):
 
 def conv_gn_relu(x, weight, gamma, beta, groups, stride=1):
     return ConvGNReLUFn.apply(x, weight, gamma, beta, groups, stride)
+
+
+class MSDASampleFn(torch.autograd.Function):
+    """The sampling core of multi-scale deformable attention, forward (`vkn_msda_sample_f32`, include/vkn_msda.h) and backward
+    (`vkn_msda_sample_bwd_f32`, include/vkn_msda_train.h) on the library's kernels.  The RAW offsets and logits go in: the softmax and
+    its backward are inside the kernels.  Only the operands are saved; the backward recomputes the forward's points.  No float atomics:
+    two backward passes give the same bits.  `ref` and the shapes get no gradient.  A non-finite gradient is reported through
+    `ops.workspace_status`."""
+
+    @staticmethod
+    def forward(ctx, value, offsets, logits, ref, spatial_shapes, num_heads, num_points):
+        value = value.contiguous()
+        ctx.save_for_backward(value, offsets, logits, ref)
+        ctx.cfg = (tuple((int(h), int(w)) for h, w in spatial_shapes), int(num_heads), int(num_points))
+        ctx.ws_cache = ops.workspace_cache()      # the backward reports into the status word of the thread that ran the forward
+        return ops.msda_sample(value, ctx.cfg[0], offsets, logits, ref, ctx.cfg[1], ctx.cfg[2])
+
+    @staticmethod
+    def backward(ctx, dout):
+        value, offsets, logits, ref = ctx.saved_tensors
+        shapes, M, P = ctx.cfg
+        with ops.adopt_workspace(ctx.ws_cache):
+            dvalue, doff, dlogits = ops.msda_sample_bwd(value, shapes, offsets, logits, ref, dout.contiguous(), M, P)
+        need = ctx.needs_input_grad
+        return dvalue if need[0] else None, doff if need[1] else None, dlogits if need[2] else None, None, None, None, None
+
+
+def msda_sample(value, spatial_shapes, offsets, logits, ref, num_heads, num_points):
+    """value [B, S, M D]; offsets [B Q, 2 M L P] and logits [B Q, M L P], the raw outputs of the `sampling_offsets` /
+    `attention_weights` Linears (column ranges of one GEMM output are taken as they are); ref [Q, L, 2] -> [B, Q, M D], differentiable
+    in value, offsets and logits."""
+    return MSDASampleFn.apply(value, offsets, logits, ref, spatial_shapes, num_heads, num_points)

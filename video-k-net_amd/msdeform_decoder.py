@@ -10,7 +10,10 @@ Two forward paths, in the manner of `SemanticFPNWrapper`:
   * `forward_fused`: the encoder batch-first on [B Q][C] rows through this library: per layer one `vkn_linear_f32` for offsets and
     logits together, one for `value_proj`, the sampling core `vkn_msda_sample_f32` (include/vkn_msda.h), `output_proj`,
     `vkn_layernorm_act_fwd_f32` with the residual, the FFN as two linears, the second LayerNorm.  The 1x1 `input_convs` (Cin up to
-    2048), the lateral / output convs and `mask_feature` stay torch ops.  There is no HIP backward of the core.
+    2048), the lateral / output convs and `mask_feature` stay torch ops.
+With `fused_backward=True` (an extra keyword, off by default) the sampling core inside `forward_torch` is `autograd.msda_sample` when
+a gradient is needed: forward `vkn_msda_sample_f32`, backward `vkn_msda_sample_bwd_f32` (include/vkn_msda_train.h), deterministic
+and free of float atomics; the Linears, LayerNorms, convs and transposes around it stay torch autograd.
 Whatever no shipped config uses raises NotImplementedError at construction.
 """
 import math
@@ -19,7 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import autograd, ops
 from .registry import NECKS
 from .semantic_fpn import SinePositionalEncoding
 
@@ -67,7 +70,9 @@ def msda_core_torch(value, spatial_shapes, sampling_locations, attention_weights
 
 class MultiScaleDeformableAttention(nn.Module):
     """mmcv 1.x `MultiScaleDeformableAttention` (mmcv/ops/multi_scale_deform_attn.py) for the decoder's call: seq-first, all-valid
-    padding mask, 2-d reference points.  `forward` is the torch composition; the decoder's fused path reads the parameters."""
+    padding mask, 2-d reference points.  `forward` is the torch composition; the decoder's fused path reads the parameters.
+    `fused_backward` (an attribute the decoder sets, no ctor argument): when a gradient is needed on CUDA fp32 tensors inside the
+    core's envelope, the sampling core runs as `autograd.msda_sample` on the raw offsets and logits."""
 
     def __init__(self, embed_dims=256, num_heads=8, num_levels=4, num_points=4, im2col_step=64, dropout=0.1, batch_first=False,
                  norm_cfg=None, init_cfg=None):
@@ -82,6 +87,7 @@ class MultiScaleDeformableAttention(nn.Module):
             _unsupported(f'attention norm_cfg={norm_cfg!r}')
         self.embed_dims, self.num_heads, self.num_levels, self.num_points = embed_dims, num_heads, num_levels, num_points
         self.im2col_step, self.batch_first = im2col_step, batch_first
+        self.fused_backward = False
         self.sampling_offsets = nn.Linear(embed_dims, num_heads * num_levels * num_points * 2)
         self.attention_weights = nn.Linear(embed_dims, num_heads * num_levels * num_points)
         self.value_proj = nn.Linear(embed_dims, embed_dims)
@@ -113,12 +119,31 @@ class MultiScaleDeformableAttention(nn.Module):
         M, L, P = self.num_heads, self.num_levels, self.num_points
         value = self.value_proj(value.permute(1, 0, 2)).view(B, Q, M, C // M)
         query = query.permute(1, 0, 2)
-        offsets = self.sampling_offsets(query).view(B, Q, M, L, P, 2)
-        weights = self.attention_weights(query).view(B, Q, M, L * P).softmax(-1).view(B, Q, M, L, P)
+        raw_offsets, raw_logits = self.sampling_offsets(query), self.attention_weights(query)
+        if self._fused_backward_ok(value, raw_offsets, raw_logits, reference_points, spatial_shapes):
+            core = autograd.msda_sample(value.reshape(B, Q, C), spatial_shapes, raw_offsets.reshape(B * Q, -1), raw_logits.reshape(B * Q, -1),
+                                        reference_points.contiguous(), M, P)
+            return self.output_proj(core).permute(1, 0, 2) + identity
+        offsets = raw_offsets.view(B, Q, M, L, P, 2)
+        weights = raw_logits.view(B, Q, M, L * P).softmax(-1).view(B, Q, M, L, P)
         normalizer = query.new_tensor([[int(w), int(h)] for h, w in spatial_shapes])
         locations = reference_points[None, :, None, :, None, :] + offsets / normalizer[None, None, None, :, None, :]
         out = self.output_proj(msda_core_torch(value, spatial_shapes, locations, weights)).permute(1, 0, 2)
         return out + identity
+
+
+    def _fused_backward_ok(self, value, raw_offsets, raw_logits, reference_points, spatial_shapes):
+        """the flag, a gradient to compute, CUDA fp32 operands, the envelope of the core and of its backward"""
+        ts = (value, raw_offsets, raw_logits)
+        if not (self.fused_backward and torch.is_grad_enabled() and any(t.requires_grad for t in ts)):
+            return False
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in ts + (reference_points,)):
+            return False
+        B, Q, M, D = value.shape
+        L, P = self.num_levels, self.num_points
+        if len(spatial_shapes) != L or tuple(reference_points.shape) != (Q, L, 2) or not ops.msda_fits(M, D, L, P):
+            return False
+        return ops.msda_bwd_workspace_bytes(spatial_shapes, B, Q, M, D, P) > 0
 
 
 class _FFN(nn.Module):
@@ -217,13 +242,15 @@ _ENCODER_DEFAULT = dict(
 
 
 class MSDeformAttnPixelDecoder(nn.Module):
-    """knet/det/msdeformattn_decoder.py:18-275.  `fused` (an extra keyword) = False keeps every call on `forward_torch`."""
+    """knet/det/msdeformattn_decoder.py:18-275.  `fused` (an extra keyword) = False keeps every call on `forward_torch`;
+    `fused_backward` (another) = True gives `forward_torch` the library's sampling core with its HIP backward where a gradient is needed."""
 
     def __init__(self, in_channels=[256, 512, 1024, 2048], strides=[4, 8, 16, 32], feat_channels=256, out_channels=256, num_outs=3,
                  return_one_list=True, norm_cfg=dict(type='GN', num_groups=32), act_cfg=dict(type='ReLU'), encoder=_ENCODER_DEFAULT,
-                 positional_encoding=dict(type='SinePositionalEncoding', num_feats=128, normalize=True), init_cfg=None, fused=True):
+                 positional_encoding=dict(type='SinePositionalEncoding', num_feats=128, normalize=True), init_cfg=None, fused=True,
+                 fused_backward=False):
         super().__init__()
-        self.fused = bool(fused)
+        self.fused, self.fused_backward = bool(fused), bool(fused_backward)
         if norm_cfg is None or _get(norm_cfg, 'type') != 'GN':
             _unsupported(f'norm_cfg={norm_cfg!r} (GN only)')
         if act_cfg is None or _get(act_cfg, 'type') != 'ReLU':
@@ -239,6 +266,8 @@ class MSDeformAttnPixelDecoder(nn.Module):
         self.return_one_list = return_one_list
         self.encoder = _Encoder(**enc)
         self.num_encoder_levels = self.encoder.layers[0].attentions[0].num_levels
+        for layer in self.encoder.layers:
+            layer.attentions[0].fused_backward = self.fused_backward
         assert self.num_encoder_levels >= 1, 'num_levels in attn_cfgs must be at least one'
         if self.num_encoder_levels > self.num_input_levels:
             raise ValueError(f'{self.num_encoder_levels} encoder levels from {self.num_input_levels} inputs')

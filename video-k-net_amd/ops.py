@@ -1643,6 +1643,57 @@ def msda_sample(value, spatial_shapes, offsets, logits, ref, num_heads, num_poin
     return out
 
 
+def _msda_shapes(spatial_shapes):
+    return (ctypes.c_int * (2 * len(spatial_shapes)))(*[int(v) for hw in spatial_shapes for v in hw])
+
+
+def msda_bwd_workspace_bytes(spatial_shapes, B, Q, num_heads, head_dim, num_points):
+    """vkn_msda_bwd_workspace_bytes (include/vkn_msda_train.h): the bytes `msda_sample_bwd` needs, 0 outside its envelope"""
+    return int(_lib.lib().vkn_msda_bwd_workspace_bytes(_msda_shapes(spatial_shapes), int(B), int(Q), int(num_heads), int(head_dim),
+                                                       len(spatial_shapes), int(num_points)))
+
+
+def msda_sample_bwd(value, spatial_shapes, offsets, logits, ref, dout, num_heads, num_points, grad_rows=None):
+    """The backward of `msda_sample` (include/vkn_msda_train.h: vkn_msda_sample_bwd_f32) from its own operands and the gradient
+    dout [B, Q, M D] of its output -> (dvalue [B, S, M D], doff [B Q, 2 M L P], dlogits [B Q, M L P]).  No float atomics: two calls give
+    the same bits.  `grad_rows`: an optional [B Q, 3 M L P] fp32 buffer that receives doff | dlogits side by side (the mirror of the
+    forward's one GEMM output); the two gradients returned are then its column ranges.  A non-finite dout or contribution is reported
+    through `workspace_status`."""
+    value, ref, dout = _req(value, 'value'), _req(ref, 'ref'), _req(dout, 'dout')
+    B, S, C = value.shape
+    M, P, L = int(num_heads), int(num_points), len(spatial_shapes)
+    Q = ref.shape[0]
+    if C % M or tuple(ref.shape) != (Q, L, 2) or sum(int(h) * int(w) for h, w in spatial_shapes) != S or tuple(dout.shape) != (B, Q, C):
+        raise ValueError(f'msda_sample_bwd: value {tuple(value.shape)}, ref {tuple(ref.shape)}, dout {tuple(dout.shape)}, levels '
+                         f'{list(spatial_shapes)}, {M} heads do not fit')
+    n_off, n_log = 2 * M * L * P, M * L * P
+    offsets, ld_off = _req_rows(offsets, 'offsets', n_off)
+    logits, ld_logits = _req_rows(logits, 'logits', n_log)
+    if offsets.shape[0] != B * Q or logits.shape[0] != B * Q:
+        raise ValueError(f'msda_sample_bwd: {offsets.shape[0]} offset rows, {logits.shape[0]} logit rows for B Q = {B * Q}')
+    dev = value.device
+    if grad_rows is None:
+        doff = torch.empty((B * Q, n_off), dtype=torch.float32, device=dev)
+        dlogits = torch.empty((B * Q, n_log), dtype=torch.float32, device=dev)
+    else:
+        if (not torch.is_tensor(grad_rows) or grad_rows.dtype != torch.float32 or grad_rows.device != dev or not grad_rows.is_contiguous()
+                or tuple(grad_rows.shape) != (B * Q, n_off + n_log) or grad_rows.data_ptr() % 16):
+            raise ValueError(f'msda_sample_bwd: grad_rows must be a contiguous, 16-byte aligned fp32 [{B * Q}, {n_off + n_log}] on {dev}')
+        doff, dlogits = grad_rows[:, :n_off], grad_rows[:, n_off:]
+    L_ = _lib.lib()
+    shapes = _msda_shapes(spatial_shapes)
+    nb = L_.vkn_msda_bwd_workspace_bytes(shapes, B, Q, M, C // M, L, P)
+    if not nb:
+        raise ValueError('msda_sample_bwd: shape outside the envelope')
+    dvalue = torch.empty_like(value)
+    ws = _workspace(nb, dev)
+    with torch.cuda.device(dev):
+        check(L_.vkn_msda_sample_bwd_f32(_ptr(value), _ptr(offsets), ld_off, _ptr(logits), ld_logits, _ptr(ref), shapes, _ptr(dout),
+                                         _ptr(dvalue), _ptr(doff), doff.stride(0), _ptr(dlogits), dlogits.stride(0), B, Q, M, C // M, L, P,
+                                         _ptr(ws), ws.numel(), _stream()))
+    return dvalue, doff, dlogits
+
+
 def layernorm_act(x, gamma, beta, resid=None, eps=1e-5, act=0):
     """act(LayerNorm(x + resid) gamma + beta) per row of [rows, C <= 256] (include/vkn.h: vkn_layernorm_act_fwd_f32), no gradient"""
     x = _req(x, 'x')
