@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libvkn.so')
-SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_segloss.hip', 'vkn_stq.hip', 'vkn_vpq.hip', 'vkn_fpn_bwd.hip', 'vkn_msda.hip', 'vkn_msda_bwd.hip', 'vkn_api.hip')
+SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_segloss.hip', 'vkn_stq.hip', 'vkn_vpq.hip', 'vkn_fpn_bwd.hip', 'vkn_msda.hip', 'vkn_msda_bwd.hip', 'vkn_rle.hip', 'vkn_api.hip')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 # The C ABI, one header per part, each behind the headers it #includes.  A new part is one more name here.
 ABI_HEADERS = ('vkn.h', 'vkn_track.h', 'vkn_track_train.h', 'vkn_gt.h', 'vkn_decode.h')
@@ -34,6 +34,9 @@ NECK_HEADERS = ('vkn_msda.h',)
 # Neck training parts: a seventh such table `ABI_NECK_TRAIN` behind the six, on the same terms; its constants in their own record
 # `MSDA_TRAIN`.  `_each`'s DEFAULT stays the six tables before it: the loops that bind go over `_bound`, the six and this one.
 NECK_TRAIN_HEADERS = ('vkn_msda_train.h',)
+# Result parts: an eighth such table `ABI_RESULT` behind the seven, on the same terms; its constants in their own record `RLE`.  `_bound`
+# stays the seven tables before it: the loops that bind go over `_every`, the seven and this one.
+RESULT_HEADERS = ('vkn_rle.h',)
 
 
 class VknLibraryError(RuntimeError):
@@ -147,7 +150,12 @@ def _bound(field):
     return _each(field) + _each(field, (ABI_NECK_TRAIN,))
 
 
-_EVERY_HEADER = ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS + TRAIN_HEADERS + NECK_HEADERS + NECK_TRAIN_HEADERS
+def _every(field):
+    """`_bound`'s seven tables, then `ABI_RESULT`: every table that is bound"""
+    return _bound(field) + _each(field, (ABI_RESULT,))
+
+
+_EVERY_HEADER = ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS + TRAIN_HEADERS + NECK_HEADERS + NECK_TRAIN_HEADERS + RESULT_HEADERS
 _ALL = read_abi(INCLUDE, _EVERY_HEADER)          # ONE reading: includes resolve, a name declared twice is an error
 ABI = {h: _ALL[h] for h in ABI_HEADERS}
 ABI_EXT = {h: _ALL[h] for h in EXTENSION_HEADERS}
@@ -156,6 +164,7 @@ ABI_WINDOW_METRIC = {h: _ALL[h] for h in WINDOW_METRIC_HEADERS}
 ABI_TRAIN = {h: _ALL[h] for h in TRAIN_HEADERS}
 ABI_NECK = {h: _ALL[h] for h in NECK_HEADERS}
 ABI_NECK_TRAIN = {h: _ALL[h] for h in NECK_TRAIN_HEADERS}
+ABI_RESULT = {h: _ALL[h] for h in RESULT_HEADERS}
 HEADER, PROTOS, SYMBOLS, STRUCTS, MIRRORS = (getattr(ABI['vkn.h'], k) for k in ('path', 'protos', 'symbols', 'structs', 'mirrors'))
 CONSTS = {k: v for _, k, v in _each('consts', (ABI,))}      # every ABI header's constants: no name is declared twice
 SEG = ABI_EXT['vkn_seg_loss.h'].consts              # an extension's constants stay in its own record
@@ -164,6 +173,7 @@ VPQ = ABI_WINDOW_METRIC['vkn_vpq.h'].consts         # ... and a windowed metric 
 FPN_TRAIN = ABI_TRAIN['vkn_fpn_train.h'].consts     # ... and a training part's
 MSDA = ABI_NECK['vkn_msda.h'].consts                # ... and a neck part's
 MSDA_TRAIN = ABI_NECK_TRAIN['vkn_msda_train.h'].consts      # ... and a neck training part's
+RLE = ABI_RESULT['vkn_rle.h'].consts                # ... and a result part's
 GT_MAX_IMAGES = CONSTS['VKN_GT_MAX_IMAGES']
 GT_MAX_CLASSES = CONSTS['VKN_GT_MAX_CLASSES']
 GT_MAX_IDS = CONSTS['VKN_GT_MAX_IDS']
@@ -190,7 +200,7 @@ def _ctype(base, depth, where, result=False):
     return ctypes.c_void_p
 
 
-for _h, _name, _fields in _bound('structs'):
+for _h, _name, _fields in _every('structs'):
     _at = f'include/{_h}: {_name}'
     _ALL[_h].mirrors[_name] = _MIRROR[_name] = type(_name, (ctypes.Structure,), {
         '__doc__': f'Mirror of {_at} (device pointers as integers).',
@@ -210,7 +220,7 @@ POINTER_EXCEPTIONS = {
     ('vkn_msda_bwd_workspace_bytes', 'shapes'): ctypes.POINTER(ctypes.c_int),       # likewise
     ('vkn_msda_sample_bwd_f32', 'shapes'): ctypes.POINTER(ctypes.c_int),            # likewise
 }
-for _fn, _p in set(POINTER_EXCEPTIONS) - {(fn, q[0]) for _, fn, (_, params) in _bound('protos') for q in params}:
+for _fn, _p in set(POINTER_EXCEPTIONS) - {(fn, q[0]) for _, fn, (_, params) in _every('protos') for q in params}:
     raise VknLibraryError(f'POINTER_EXCEPTIONS names {_fn}({_p}), which none of the headers {_EVERY_HEADER} declares')
 
 DEBUG_LIBPATH = os.path.join(LIBDIR, 'libvkn_debug.so')
@@ -305,12 +315,12 @@ def lib():
         raise VknLibraryError(f'{path} is missing — run `python -c "import __graft_entry__ as g; g.build()"` '
                               '(there is deliberately no CPU fallback)')
     L = ctypes.CDLL(path)
-    for h, name, (result, params) in _bound('protos'):
+    for h, name, (result, params) in _every('protos'):
         fn, at = getattr(L, name), f'include/{h}: {name}'
         fn.restype = _ctype(*result, at, result=True)
         fn.argtypes = [POINTER_EXCEPTIONS.get((name, p)) or _ctype(base, depth, at) for p, base, depth in params]
     # header vs binary: structs are handed to the kernels verbatim, so a library built from another header means garbage pointers
-    for h, name, mirror in _bound('mirrors'):
+    for h, name, mirror in _every('mirrors'):
         probe = 'vkn_sizeof_' + re.sub(r'(?<!^)(?=[A-Z])', '_', name[3:]).lower()
         if not any(probe in hdr.protos for hdr in _ALL.values()):        # any header may declare a struct's size probe
             raise VknLibraryError(f'include/{h} declares struct {name} without its size probe {probe}()')

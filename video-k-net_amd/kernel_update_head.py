@@ -592,6 +592,22 @@ class KernelUpdateHead(nn.Module):
         seg_masks = self.rescale_masks(masks_per_img, img_meta) > self._meta(test_cfg, 'mask_thr')
         return self.segm2result(seg_masks, labels_per_img, scores_per_img)
 
+    def get_seg_masks_rle(self, masks_per_img, labels_per_img, scores_per_img, test_cfg, img_meta):
+        """`get_seg_masks` with the masks as COCO RLE dicts: what `encode_mask_results` (external/test.py:55-70) makes of its result,
+        without the K full-resolution masks ever reaching the host.  The rescale is `rescale_masks` as it is; the threshold and the
+        encoding are one device call on its fp32 output (`mask_rle.MaskRLE`, include/vkn_rle.h: set iff v > mask_thr, torch's `>`)."""
+        import numpy as np
+        from .mask_rle import default_encoder
+        rles = default_encoder()(self.rescale_masks(masks_per_img, img_meta).float(), thr=float(self._meta(test_cfg, 'mask_thr')))
+        det_labels = labels_per_img.cpu().numpy()
+        bboxes = np.zeros((len(rles), 5), dtype=np.float32)     # fake boxes: only the score column is filled
+        bboxes[:, -1] = scores_per_img.cpu().numpy()
+        bbox_result = [bboxes[det_labels == i, :] for i in range(self.num_classes)]
+        segm_result = [[] for _ in range(self.num_classes)]
+        for idx, rle in enumerate(rles):
+            segm_result[det_labels[idx]].append(rle)
+        return bbox_result, segm_result
+
     def segm2result(self, mask_preds, det_labels, cls_scores):
         """One D2H copy of the K boolean masks; per-class lists exactly as the reference builds them (:468-481)."""
         import numpy as np

@@ -177,6 +177,9 @@ class KernelUpdateHeadVideo(_QueryMerge, KernelUpdateHead):
         tracks = outs2results(bboxes=bboxes, labels=labels_per_img, masks=seg_masks, ids=ids_per_img, num_classes=self.num_classes)
         return tracks['bbox_results'], tracks['mask_results']
 
+    # the VIS head's instance results as COCO RLE dicts: the image head's method (rescale as above, threshold + encoding on the device)
+    get_seg_masks_rle = KernelUpdateHead.get_seg_masks_rle
+
 
 KernelUpdateHead.get_seg_masks_tracking = KernelUpdateHeadVideo.get_seg_masks_tracking   # the per-frame head has it too (:484)
 

@@ -1799,3 +1799,40 @@ def vpq_update(cfg, state, gt_sem, gt_ins, pred_sem, pred_ins):
     maps, B, HW = _four_maps('vpq_update', state, gt_sem, gt_ins, pred_sem, pred_ins)
     with torch.cuda.device(state.device):
         check(_lib.lib().vkn_vpq_update_i32(ctypes.byref(cfg), _ptr(state), state.numel(), *[_ptr(m) for m in maps], int(B), int(HW), _stream()))
+
+
+# ---- COCO run-length encoding of instance masks (include/vkn_rle.h): caller-owned pools
+def rle_workspace_bytes(K, H, W):
+    """vkn_rle_workspace_bytes: bytes of one call's workspace, 0 outside the envelope of include/vkn_rle.h."""
+    return int(_lib.lib().vkn_rle_workspace_bytes(int(K), int(H), int(W)))
+
+
+def rle_encode(masks, records, runs, pool, status, ws, thr=None):
+    """Encode K masks (vkn_rle_encode_u8 / vkn_rle_encode_f32, eight launches, no synchronisation).  masks: bool or uint8 [K,H,W]
+    (nonzero = set), or float32 [K,H,W] with `thr` (set iff v > thr).  records int32 [K, VKN_RLE_RECORD_INTS], runs uint32-as-int32
+    [cap_runs], pool uint8 [cap_bytes], status int32 [1] (sticky: cleared by the caller), ws uint8 [rle_workspace_bytes(K, H, W)]: CUDA
+    tensors of the caller, written in place."""
+    if torch.is_tensor(masks) and masks.is_cuda and masks.dtype == torch.float32:
+        if thr is None:
+            raise ValueError('rle_encode: float32 logits need `thr`')
+        src = _req(masks, 'masks')
+    else:
+        if thr is not None:
+            raise ValueError('rle_encode: `thr` goes with float32 logits only')
+        src = _req_bytes(masks, 'masks')
+        if src.data_ptr() % 16:
+            src = src.clone()
+    if src.dim() != 3:
+        raise ValueError(f'rle_encode: masks [K,H,W], got {tuple(src.shape)}')
+    K, H, W = src.shape
+    records, runs, status = (_req_plain(t, n, torch.int32) for t, n in ((records, 'records'), (runs, 'runs'), (status, 'status')))
+    pool, ws = _req_plain(pool, 'pool', torch.uint8), _req_plain(ws, 'ws', torch.uint8)
+    if records.numel() != K * _lib.RLE['VKN_RLE_RECORD_INTS'] or status.numel() < 1 or any(t.device != src.device for t in (records, runs, pool, status, ws)):
+        raise ValueError('rle_encode: records int32 [K, VKN_RLE_RECORD_INTS], status int32 [1], everything on the masks\' device')
+    L = _lib.lib()
+    tail = (K, H, W, _ptr(records), _ptr(runs), runs.numel(), _ptr(pool), pool.numel(), _ptr(status), _ptr(ws), ws.numel(), _stream())
+    with torch.cuda.device(src.device):
+        if thr is None:
+            check(L.vkn_rle_encode_u8(_ptr(src), *tail))
+        else:
+            check(L.vkn_rle_encode_f32(_ptr(src), float(thr), *tail))
