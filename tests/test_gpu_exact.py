@@ -128,6 +128,26 @@ def test_mask_decode(vkn, group):
     _finish(vkn, [f for f in fails if f])
 
 
+@pytest.mark.parametrize('B,znb', [(1, 1), (65, 2), (129, 0)], ids=['one_nblock', 'two_nblocks', 'off'])
+def test_mask_decode_row_split(vkn, B, znb):
+    """The few-frame row split of the decode launcher (rows over blockIdx.z) at N = 100, C = 32, P = 128: one workgroup per frame, so
+    B = 1 runs one n-block per workgroup (B G2 <= 64), B = 65 two (<= 128), B = 129 none (four n-blocks, no split).  The sweep above
+    reaches the first form only.  Which form ran is read off the launch itself: the n-blocks per workgroup are the first template
+    argument of the k_decode_mfma instantiation the profiler saw, so a change of the launcher's thresholds fails here."""
+    ops = vkn.ops
+    s = ec.Shape(B, 100, 32, 8, 16, 2000 + B, False)
+    x, k, kb, out = ec.decode_case(s)
+    xd, kd, kbd = _cuda(x, k, kb)
+    hi, lo = ops.split_planes(kd)
+    got, names = _run_and_events(lambda: ops.mask_decode_planes(xd, hi, lo, s.N, kbd))
+    nbs = [int(m.group(1)) for m in (re.search(r'k_decode_mfma(?:<|ILi)(\d+)', n) for n in names) if m]
+    assert nbs == [znb or 4], (nbs, sorted(set(names)))                    # one launch (N <= 128) of that many n-blocks per workgroup
+    fails = [_diff(f'decode planes bias {ec.sid(s)} [b, n, y, x]', got, out),
+             _diff(f'decode planes nobias {ec.sid(s)} [b, n, y, x]', ops.mask_decode_planes(xd, hi, lo, s.N), out - kb.double()[..., None, None]),
+             _diff(f'decode scaled 2^-7 {ec.sid(s)} [b, n, y, x]', ops.mask_decode(xd, kd, kbd, out_scale=torch.tensor(2.0 ** -7, device=DEV)), out * 2.0 ** -7)]
+    _finish(vkn, [f for f in fails if f])
+
+
 # ------------------------------------------------------------------------------------------------------------------- fused pass
 @pytest.mark.parametrize('group', list(GROUPS))
 def test_decode_gather(vkn, group):

@@ -34,10 +34,8 @@ __global__ __launch_bounds__(D4_THREADS, 1) void k_decode4(const float* __restri
                                                            float* __restrict__ out, int N, int NPT, int n0, int C, int P,
                                                            int px_per_wg, int xcd_remap, VknDecodeStrides fs) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int LDK = C + 8;
-    _Float16* ldsH = reinterpret_cast<_Float16*>(smem);
-    _Float16* ldsL = ldsH + NB * 32 * LDK;
-    float* kbs = reinterpret_cast<float*>(ldsL + NB * 32 * LDK);
+    DECTILE_LDS(NB, smem, C, LDK, ldsH, ldsL)  // the planes and the bias as k_decode_mfma lays them out
+    float* kbs = DECTILE_LDS_BIAS(NB, ldsL, LDK);
 
     const int b = blockIdx.y;
     const int lane = threadIdx.x & 63;

@@ -17,51 +17,12 @@
 #include "vkn_common.h"
 #include "vkn_launch.h"
 
-#define DEC_THREADS 512
-#define DEC_WAVES 8
-#define DEC_TILE 64  // pixels per wave tile: two interleaved 32-column MFMA strips (even / odd pixels)
+#include "vkn_dectile.h"
+
 #define DEC_OPT_DEFAULT 1  // round-2 variants of k_decode_mfma compiled into the release library (see OPT below)
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+using dectile::u32x2;
 typedef unsigned int u32x4w __attribute__((ext_vector_type(4)));
-
-// ---- bit-packed output (intermediate stages of the fused head): instead of the logits, emit bit(z >= thr) — all the next
-// stage's gather consumes — as words[B][P/64][2][NPT]: for 64-px tile T and row n, word [T][0][n] bit i = pixel 64 T + 2 i
-// (even pixels = MFMA strip 0) and word [T][1][n] bit i = pixel 64 T + 2 i + 1 (strip 1).  That is exactly what the two ballots of
-// a C/D register deliver, so the epilogue is 2 v_cmp + 4 selects per register pair and four 256-B row stores per tile (a first
-// version that interleaved the two ballots into pixel order on the scalar unit cost as much as the logits stores it replaced:
-// one SALU serves the whole CU).  The gather's byte -> fragment table absorbs the even/odd split.
-// Cuts the stage hand-off from 2 x 15.3 MB to 2 x 0.5 MB per frame.
-template <int NB>
-__device__ __forceinline__ void dec_emit_bits(const f32x16 (&acc)[2][NB], float thr, unsigned* __restrict__ wbase, int NPT,
-                                              int lane) {
-    constexpr int NH = (NB * 32 + 63) / 64;
-    int w[2][NH];  // [even | odd pixels][row half]: lane = row & 63
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int h = 0; h < NH; ++h) w[t][h] = 0;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const unsigned long long m0 = __ballot(acc[0][nb][r] >= thr);  // even pixels: bit 32 g + li
-            const unsigned long long m1 = __ballot(acc[1][nb][r] >= thr);  // odd pixels
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                const int row = nb * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;  // compile-time
-                const bool mine = lane == (row & 63);                      // lane <- its row's words (values are wave-uniform)
-                w[0][row >> 6] = mine ? (int)(unsigned)(m0 >> (32 * g)) : w[0][row >> 6];
-                w[1][row >> 6] = mine ? (int)(unsigned)(m1 >> (32 * g)) : w[1][row >> 6];
-            }
-            __builtin_amdgcn_sched_barrier(0);  // keep each pair of ballots next to its selects (else 128 masks spill SGPRs)
-        }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int h = 0; h < NH; ++h)
-            if (h * 64 + lane < NB * 32) wbase[(size_t)t * NPT + h * 64 + lane] = (unsigned)w[t][h];
-}
 
 // ABL (ablation, debugging only; selected by env VKN_DECODE_ABL): 0 = the real kernel, 1 = no MFMA, 2 = no x loads,
 // 3 = no output stores.  Variants 1-3 produce WRONG results by construction and exist to attribute time.
@@ -77,7 +38,7 @@ __device__ __forceinline__ void dec_emit_bits(const f32x16 (&acc)[2][NB], float 
 // multiplied by the device scalar *oscale before it is stored — instead of a second pass over the result.  The inference
 // instantiations (OSC = 0) are the kernels they were.
 template <int NB, int ABL, int RING, int BITS, int OPT, int XH = 0, int OSC = 0>
-__global__ __launch_bounds__(DEC_THREADS, 2) void k_decode_mfma(
+__global__ __launch_bounds__(dectile::THREADS, 2) void k_decode_mfma(
     const float* __restrict__ x, const _Float16* __restrict__ kfh, const _Float16* __restrict__ kfl,
     const float* __restrict__ kb, float* __restrict__ out, int N, int NPT, int n0, int C, int P, int px_per_wg,
     int xcd_remap, VknDecodeStrides fs, unsigned* __restrict__ bits_out, float thr, const float* __restrict__ oscale) {
@@ -85,48 +46,20 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode_mfma(
 #define DEC_V(v) (OSC ? (v) * osc_ : (v))
     n0 += (int)blockIdx.z * NB * 32;   // few frames per launch: the kernel rows are spread over gridDim.z workgroups per pixel range (round 5)
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int LDK = C + 8;  // halfs per LDS row; (C+8)*2 B = odd multiple of 16 B -> b128 reads conflict-free
-    _Float16* ldsH = reinterpret_cast<_Float16*>(smem);
-    _Float16* ldsL = ldsH + NB * 32 * LDK;
+    DECTILE_LDS(NB, smem, C, LDK, ldsH, ldsL)
 
     const int b = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // provably wave-uniform -> scalar control flow
     const int g = lane >> 5, li = lane & 31;
 
-    float* kbs = reinterpret_cast<float*>(ldsL + NB * 32 * LDK);
+    float* kbs = DECTILE_LDS_BIAS(NB, ldsL, LDK);
     auto stage_planes = [&]() {
         // ---- stage this frame's kernels (rows n0 .. n0+NB*32) into LDS
         {
             const _Float16* gh = kfh + (size_t)b * fs.plane + (size_t)n0 * C;
             const _Float16* gl = kfl + (size_t)b * fs.plane + (size_t)n0 * C;
-            const int cpr = C >> 3;
-            // FOUR iterations' loads (8 x 16 bytes per thread) are requested before the first LDS store: the rolled load -> store loop
-            // was one memory round trip per iteration — eight in a row at C = 256, most of this kernel's time at one frame per launch
-            const int items = NB * 32 * cpr;
-            for (int i0 = threadIdx.x; i0 < items; i0 += 4 * DEC_THREADS) {
-                half8 vh[4], vl[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int i = i0 + u * DEC_THREADS;
-                    const int r = i / cpr, q = i - r * cpr;
-                    vh[u] = half8{0, 0, 0, 0, 0, 0, 0, 0};
-                    vl[u] = half8{0, 0, 0, 0, 0, 0, 0, 0};
-                    if (i < items && n0 + r < N) {  // rows >= N of the planes are never written by the producer: treat as zero
-                        vh[u] = *reinterpret_cast<const half8*>(gh + (size_t)r * C + q * 8);
-                        vl[u] = *reinterpret_cast<const half8*>(gl + (size_t)r * C + q * 8);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int i = i0 + u * DEC_THREADS;
-                    if (i < items) {
-                        const int r = i / cpr, q = i - r * cpr;
-                        *reinterpret_cast<half8*>(ldsH + r * LDK + q * 8) = vh[u];
-                        *reinterpret_cast<half8*>(ldsL + r * LDK + q * 8) = vl[u];
-                    }
-                }
-            }
+            DECTILE_STAGE_PLANES(NB, ldsH, ldsL, LDK, C, gh, gl, threadIdx.x, n0 + r_ < N)
         }
         // folded decode bias of the chunk's rows -> LDS (accumulators start from it)
         if (threadIdx.x < NB * 32) {
@@ -142,8 +75,8 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode_mfma(
     if (xcd_remap && (gridDim.x % 8) == 0) gx = (gx % 8) * (gridDim.x / 8) + gx / 8;
     const int p_begin = gx * px_per_wg;
     const int p_end = min(P, p_begin + px_per_wg);
-    const int ntile = (p_end > p_begin) ? (p_end - p_begin + DEC_TILE - 1) / DEC_TILE : 0;
-    const int my = (ntile > wave) ? (ntile - wave + DEC_WAVES - 1) / DEC_WAVES : 0;
+    const int ntile = (p_end > p_begin) ? (p_end - p_begin + dectile::TILE - 1) / dectile::TILE : 0;
+    const int my = dectile::my_tiles(ntile, wave);
     const int KS = C >> 4;
     const int total = my * KS;
     if (total == 0) {
@@ -154,8 +87,6 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode_mfma(
 
     // Buffer descriptors built from uniform values only: loads/stores are `buffer_* v, v_off, s[rsrc], s_off offen` with ONE
     // per-lane VGPR offset and every row / tile offset in the SGPR operand (no per-load VALU address arithmetic).
-    // NOTE: hipcc (ROCm 7.2) miscompiles `__builtin_bit_cast(T, vec[i])` on an ext_vector ELEMENT (always yields element 0,
-    // tools/scratch/buftest.hip) — elements are copied to scalars first and converted with __uint_as_float / __float_as_uint.
     const __amdgpu_buffer_rsrc_t xrs =
         XH ? __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(reinterpret_cast<const unsigned short*>(x) + (size_t)b * C * P), 0,
                                                C * P * 2, 0x00020000)
@@ -171,7 +102,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode_mfma(
     // is clamped into the row (such lanes are never stored).
 #define DEC_LOAD(REG)                                                                                            \
     do { /* unconditional: past the end it re-reads the last fragment (keeps vmcnt counting exact) */            \
-        const int p0_ = p_begin + (wave + DEC_WAVES * ld_sl) * DEC_TILE;                                         \
+        const int p0_ = DECTILE_TILE_P0(p_begin, wave, ld_sl);                                                   \
         const int voff_ = (((g << 3) * P + min(2 * li, max(P - 2 - p0_, 0))) << (XH ? 1 : 2));                   \
         const int soff_ = ((ld_ks << 4) * P + p0_) << (XH ? 1 : 2);                                              \
         if (XH && (OPT & 8)) { /* half storage, paired lanes (debug A/B): lane li loads 4 px x 4 channels (8 B), see DEC_COMPUTE */ \
@@ -195,28 +126,17 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode_mfma(
                          : VKN_ABL_IS(ABL, 9) ? __builtin_amdgcn_raw_buffer_load_b64(xrs, voff_, soff_ + ((e * P) << 2), 19) /* sc0 sc1 nt */ \
                                       : __builtin_amdgcn_raw_buffer_load_b64(xrs, voff_, soff_ + ((e * P) << 2), 3); \
         }                                                                                                        \
-        const bool adv_ = (ld_cnt + 1 < total);                                                                  \
-        const bool wrap_ = (ld_ks + 1 == KS);                                                                    \
-        ld_cnt += adv_ ? 1 : 0;                                                                                  \
-        ld_sl += (adv_ && wrap_) ? 1 : 0;                                                                        \
-        ld_ks = adv_ ? (wrap_ ? 0 : ld_ks + 1) : ld_ks;                                                          \
+        DECTILE_ADVANCE_LOAD(ld_ks, ld_sl, ld_cnt, total, KS)                                                    \
     } while (0)
 
 #define DEC_COMPUTE(REG)                                                                                          \
     do {                                                                                                          \
-        if (c_ks == 0) {                                                                                          \
-            _Pragma("unroll") for (int nb = 0; nb < NB; ++nb)                                                     \
-                _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                  \
-                    const float kb_ = kbs[nb * 32 + vkn_cd_row(r, lane)];                                         \
-                    acc[0][nb][r] = kb_;                                                                          \
-                    acc[1][nb][r] = kb_;                                                                          \
-                }                                                                                                 \
-        }                                                                                                         \
+        if (c_ks == 0) { DECTILE_BIAS_ACC(acc, NB, kbs, lane) }                                                   \
         half8 bh0, bl0, bh1, bl1;                                                                                 \
-        _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                           \
-            _Float16 h_, l_;                                                                                      \
-            unsigned u0_ = REG[e][0], u1_ = REG[e][1];                                                            \
-            if (XH && (OPT & 8)) { /* lanes 2j / 2j+1 hold channels 0-3 / 4-7 of pixels 4j..4j+3: swap halves via DPP */ \
+        if (!XH) { DECTILE_SPLIT_PAIR(REG, bh0, bl0, bh1, bl1) }                                                  \
+        else { _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                    \
+            unsigned u0_ = REG[e][0];                                                                             \
+            if (OPT & 8) { /* lanes 2j / 2j+1 hold channels 0-3 / 4-7 of pixels 4j..4j+3: swap halves via DPP */ \
                 const int e4_ = e & 3, odd_ = li & 1;                                                             \
                 const unsigned own0_ = REG[e4_][0], own1_ = REG[e4_][1];                                          \
                 const unsigned recv_ = (unsigned)__builtin_amdgcn_mov_dpp((int)(odd_ ? own0_ : own1_), 0xB1, 0xF, 0xF, true); \
@@ -225,18 +145,11 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode_mfma(
             if (XH == 1) { /* fp16 pair: low half = even pixel */                                                 \
                 bh0[e] = __builtin_bit_cast(_Float16, (unsigned short)(u0_ & 0xFFFFu));                           \
                 bh1[e] = __builtin_bit_cast(_Float16, (unsigned short)(u0_ >> 16));                               \
-            } else if (XH == 2) { /* bf16 pair -> fp32 (exact) -> f16 */                                          \
+            } else { /* bf16 pair -> fp32 (exact) -> f16 */                                                       \
                 bh0[e] = (_Float16)__uint_as_float(u0_ << 16);                                                    \
                 bh1[e] = (_Float16)__uint_as_float(u0_ & 0xFFFF0000u);                                            \
-            } else {                                                                                              \
-                vkn_split_f16(__uint_as_float(u0_), h_, l_);                                                      \
-                bh0[e] = h_;                                                                                      \
-                bl0[e] = l_;                                                                                      \
-                vkn_split_f16(__uint_as_float(u1_), h_, l_);                                                      \
-                bh1[e] = h_;                                                                                      \
-                bl1[e] = l_;                                                                                      \
             }                                                                                                     \
-        }                                                                                                         \
+        } }                                                                                                       \
         const int cb_ = (c_ks << 4) + (g << 3);                                                                   \
         _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) {                                                       \
             const _Float16* ap_ = ldsH + (nb * 32 + li) * LDK + cb_;                                              \
@@ -244,29 +157,23 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode_mfma(
             const half8 al = *reinterpret_cast<const half8*>(ap_ + NB * 32 * LDK);                                \
             if (VKN_ABL_IS(ABL, 1)) {                                                                                   \
                 asm volatile("" ::"v"(ah), "v"(al), "v"(bh0), "v"(bl0), "v"(bh1), "v"(bl1));                      \
-            } else { /* alternate the two accumulators so dependent MFMAs are never back to back */               \
+            } else if (XH) { /* the low half of x is zero: mfma6 without its two x_lo terms */                    \
                 acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh0, acc[0][nb], 0, 0, 0);                \
                 acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh1, acc[1][nb], 0, 0, 0);                \
-                if (!XH) {                                                                                        \
-                    acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl0, acc[0][nb], 0, 0, 0);            \
-                    acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl1, acc[1][nb], 0, 0, 0);            \
-                }                                                                                                 \
                 acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh0, acc[0][nb], 0, 0, 0);                \
                 acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh1, acc[1][nb], 0, 0, 0);                \
+            } else {                                                                                              \
+                dectile::mfma6(ah, al, bh0, bl0, bh1, bl1, acc[0][nb], acc[1][nb]);                               \
             }                                                                                                     \
         }                                                                                                         \
         if (++c_ks == KS) {                                                                                       \
-            const int p0_ = p_begin + (wave + DEC_WAVES * c_sl) * DEC_TILE;                                       \
+            const int p0_ = DECTILE_TILE_P0(p_begin, wave, c_sl);                                                 \
             const int px_ = p0_ + 2 * li;                                                                         \
-            const int vst_ = ((4 * g) * P + 2 * li) << 2;                                                         \
-            /* the 64 row offsets row * P * 4 are loop invariants the compiler would keep in 64 SGPRs (-> 230 SGPR spills as   */ \
-            /* v_writelane / v_readlane pairs in this loop); an opaque copy of P makes it recompute them per store: one s_mul   */ \
-            int Pq_ = P;                                                                                          \
-            asm volatile("" : "+s"(Pq_));                                                                         \
+            DECTILE_ROW_OFFSETS(vst_, Pq_, P, g, li)                                                              \
             if (BITS) { /* P % 64 == 0 (launcher): every tile is whole */                                        \
-                dec_emit_bits<NB>(acc, thr, bits_out + ((size_t)b * (P >> 5) + ((p0_ >> 6) << 1)) * NPT + n0, NPT, lane);   \
+                dectile::emit_bits<NB>(acc, thr, bits_out + ((size_t)b * (P >> 5) + ((p0_ >> 6) << 1)) * NPT + n0, NPT, lane);   \
             } else if (!VKN_ABL_IS(ABL, 3) || acc[0][0][0] == 12345.678f) {                                                  \
-                if (p0_ + DEC_TILE <= p_end) { /* whole tile in range (uniform): 8-byte stores, 256 B per row */  \
+                if (p0_ + dectile::TILE <= p_end) { /* whole tile in range (uniform): 8-byte stores, 256 B per row */  \
                     _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) {                                           \
                         if ((OPT & 4) && n0 + nb * 32 + 32 <= N) { /* 16-byte stores: lanes 2j / 2j+1 swap halves */ \
                             const int q_ = li & 1;                                                                \
@@ -284,19 +191,11 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode_mfma(
                                 v_[1] = q_ ? (unsigned)t1_ : __float_as_uint(e1_);                                \
                                 v_[2] = q_ ? __float_as_uint(o0_) : (unsigned)t0_;                                \
                                 v_[3] = q_ ? __float_as_uint(o1_) : (unsigned)t1_;                                \
-                                __builtin_amdgcn_raw_buffer_store_b128(v_, ors, vw_, (row_ * Pq_ + p0_) << 2, 0);   \
+                                __builtin_amdgcn_raw_buffer_store_b128(v_, ors, vw_, (row_ * Pq_ + p0_) << 2, 0);    \
                             }                                                                                     \
-                        } else { /* no per-row guard: `ors` covers exactly the frame's N rows, so the stores of rows >= N */ \
-                                 /* (ragged last n-block) are dropped by the buffer's range check — no exec branches in the loop */ \
-                            _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                      \
-                                const int row_ = n0 + nb * 32 + (r & 3) + 8 * (r >> 2);                           \
-                                const float a0_ = DEC_V(acc[0][nb][r]), a1_ = DEC_V(acc[1][nb][r]);               \
-                                const u32x2 v_ = {__float_as_uint(a0_), __float_as_uint(a1_)};                    \
-                                if (VKN_ABL_IS(ABL, 5))                                                              \
-                                    __builtin_amdgcn_raw_buffer_store_b64(v_, ors, vst_, (row_ * Pq_ + p0_) << 2, 2); \
-                                else                                                                              \
-                                    __builtin_amdgcn_raw_buffer_store_b64(v_, ors, vst_, (row_ * Pq_ + p0_) << 2, 0); \
-                            }                                                                                     \
+                        } else { /* `ors` covers exactly the frame's N rows: the stores of rows >= N are dropped */ \
+                            if (VKN_ABL_IS(ABL, 5)) DECTILE_STORE_ROWS(acc[0][nb], acc[1][nb], ors, vst_, Pq_, n0 + nb * 32, p0_, 2, OSC, osc_) \
+                            else DECTILE_STORE_ROWS(acc[0][nb], acc[1][nb], ors, vst_, Pq_, n0 + nb * 32, p0_, 0, OSC, osc_) \
                         }                                                                                         \
                     }                                                                                             \
                 } else { /* ragged tile at the end of the range: per-pixel guards, 4-byte buffer stores */        \
@@ -307,9 +206,9 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode_mfma(
                             if (row_ + 4 * g < N) {                                                               \
                                 const float a0_ = DEC_V(acc[0][nb][r]), a1_ = DEC_V(acc[1][nb][r]);               \
                                 if (px_ < p_end)                                                                  \
-                                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a0_), ors, vst_, so_, 0); \
+                                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a0_), ors, vst_, so_, 0);    \
                                 if (px_ + 1 < p_end)                                                              \
-                                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a1_), ors, vst_ + 4, so_, 0); \
+                                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a1_), ors, vst_ + 4, so_, 0);    \
                             }                                                                                     \
                         }                                                                                         \
                     }                                                                                             \
@@ -486,7 +385,7 @@ static int decode_launch(const float* x, const _Float16* kfh, const _Float16* kf
     }
     for (int n0 = 0; n0 < NPT; n0 += 128) {
         const int nb = znb ? znb : ((NPT - n0 >= 128) ? 4 : (NPT - n0) / 32);
-        const size_t lds = (size_t)2 * nb * 32 * (C + 8) * sizeof(_Float16) + (size_t)nb * 32 * sizeof(float);
+        const size_t lds = dectile::lds_bytes(nb, C);
         dim3 grid(G2, B, znb ? NPT / (znb * 32) : 1);
 #ifdef VKN_DEBUG
         if (wide) {
@@ -509,7 +408,7 @@ static int decode_launch(const float* x, const _Float16* kfh, const _Float16* kf
             continue;
         }
 #endif
-        dim3 block(DEC_THREADS);
+        dim3 block(dectile::THREADS);
 #define DEC_LAUNCH_X(NBV, ABLV, RINGV, BITSV, OPTV, XHV)                                                       \
     do {                                                                                                       \
         VKN_ALLOW_FULL_LDS((k_decode_mfma<NBV, ABLV, RINGV, BITSV, OPTV, XHV>));                               \

@@ -6,6 +6,8 @@
 #include "vkn_common.h"
 #include "vkn_launch.h"
 
+#include "vkn_dectile.h"
+
 // x_feats = semantic_feats + loc_feats                                   knet/det/kernel_head.py:238-241
 __global__ __launch_bounds__(256) void k_add2(const float* __restrict__ a, const float* __restrict__ b,
                                               float* __restrict__ out, size_t n4, size_t n) {
@@ -102,23 +104,21 @@ int vkn_launch_init_finish(const float* init_w, const float* obj, const float* s
 // + a 2-D copy + k_add2 (which alone moved 3.2 GB per 32 frames) + a logits gather that read x and the logits again: 231 MB per frame;
 // now 118 MB + the bit-word gather's read of x (34 MB).
 //
-// Structure = k_decode_mfma's (persistent 512-thread workgroup, kernel planes in LDS, a wave owns 64-px tiles as two interleaved 32-column
+// Structure = k_decode_mfma's, the decode tile engine of vkn_dectile.h (persistent 512-thread workgroup, kernel planes in LDS, a wave owns 64-px tiles as two interleaved 32-column
 // MFMA strips, feature fragments straight from global memory in MFMA B layout, 8-byte buffer loads) with a fragment PAIR per k-step:
 // the same 16 channels x 2 pixels of loc and of sem.  The 128 plane rows hold init_kernels in rows [0, Np) and conv_seg in rows
 // [Np, Np + ncls): a row multiplies ONE of the two sources, so n-blocks below SLO see the loc fragments only, and in the mixed n-blocks the
 // A fragment of the other source's rows is zeroed per lane (the accumulator then adds exact zeros: same bits as the separate decodes).
 // x = loc + sem is formed from the pair in registers and stored with the loads' addressing (256-byte segments per channel row).
 // NBL = n-blocks holding thing rows, [SLO, SHI] = n-blocks holding semantic rows — compile time (no branches around accumulators).
-typedef unsigned int ip_u32x2 __attribute__((ext_vector_type(2)));
-#define IP_THREADS 512
-#define IP_WAVES 8
-#define IP_TILE 64
 
 // logits of one 64-px tile -> their tensors: row < Np: mask_preds[b][row]; semantic row j = row - Np: seg_preds[b][j] (when wanted) and,
 // with cat_stuff_mask, mask_preds[b][Np + j - num_thing] for j >= num_thing                    knet/det/kernel_head.py:222, 231-234, 255-257
 // Buffer stores: n-blocks of thing rows only take the row offset in the SGPR operand (an opaque copy of P keeps the 64 row offsets from
 // being hoisted into 64 SGPRs, as in k_decode_mfma); in the mixed n-blocks the destination row is a per-lane byte offset, and a lane
 // whose row has no destination in a tensor stores to an offset past the buffer's range — dropped by the range check, no exec branches.
+// This loop stays here, beside the engine's DECTILE_STORE_ROWS: with the thing-only n-blocks on that macro (per-lane offset from P, not
+// from the opaque copy) k_init_pass<4, 3, 3> came out 196 instructions longer (profiles/dectile_resources.txt).
 template <int NB, int SLO>
 __device__ __forceinline__ void ip_store_tile(const f32x16 (&acc)[2][NB], const InitPassArgs& A, __amdgpu_buffer_rsrc_t mrs,
                                               __amdgpu_buffer_rsrc_t srs, int p0, int li, int g, int Ntot) {
@@ -131,7 +131,7 @@ __device__ __forceinline__ void ip_store_tile(const f32x16 (&acc)[2][NB], const 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row0 = nb * 32 + (r & 3) + 8 * (r >> 2);   // this lane's row is row0 + 4 g
-            const ip_u32x2 v = {__float_as_uint(acc[0][nb][r]), __float_as_uint(acc[1][nb][r])};
+            const dectile::u32x2 v = {__float_as_uint(acc[0][nb][r]), __float_as_uint(acc[1][nb][r])};
             if (nb < SLO) {
                 __builtin_amdgcn_raw_buffer_store_b64(v, mrs, vst, (row0 * Pq + p0) << 2, 0);
             } else {
@@ -145,54 +145,21 @@ __device__ __forceinline__ void ip_store_tile(const f32x16 (&acc)[2][NB], const 
         }
 }
 
-template <int NB>
-__device__ __forceinline__ void ip_emit_bits(const f32x16 (&acc)[2][NB], float thr, unsigned* __restrict__ wbase, int NPT, int lane) {
-    // (vkn_decode.hip dec_emit_bits: lane <- the words of its row; even / odd pixels of the 64-px tile)
-    constexpr int NH = (NB * 32 + 63) / 64;
-    int w[2][NH];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int h = 0; h < NH; ++h) w[t][h] = 0;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const unsigned long long m0 = __ballot(acc[0][nb][r] >= thr);
-            const unsigned long long m1 = __ballot(acc[1][nb][r] >= thr);
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                const int row = nb * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                const bool mine = lane == (row & 63);
-                w[0][row >> 6] = mine ? (int)(unsigned)(m0 >> (32 * g)) : w[0][row >> 6];
-                w[1][row >> 6] = mine ? (int)(unsigned)(m1 >> (32 * g)) : w[1][row >> 6];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int h = 0; h < NH; ++h)
-            if (h * 64 + lane < NB * 32) wbase[(size_t)t * NPT + h * 64 + lane] = (unsigned)w[t][h];
-}
-
 template <int NBL, int SLO, int SHI>
-__global__ __launch_bounds__(IP_THREADS, 2) void k_init_pass(const InitPassArgs A) {
+__global__ __launch_bounds__(dectile::THREADS, 2) void k_init_pass(const InitPassArgs A) {
     constexpr int NB = (NBL > SHI + 1) ? NBL : SHI + 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int C = A.C, P = A.P, LDK = C + 8, KS = C >> 4;
-    _Float16* ldsH = reinterpret_cast<_Float16*>(smem);
-    _Float16* ldsL = ldsH + NB * 32 * LDK;
-    float* kbs = reinterpret_cast<float*>(ldsL + NB * 32 * LDK);
+    const int C = A.C, P = A.P, KS = C >> 4;
+    DECTILE_LDS(NB, smem, C, LDK, ldsH, ldsL)
+    float* kbs = DECTILE_LDS_BIAS(NB, ldsL, LDK);
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, li = lane & 31;
     const int Ntot = A.Np + A.ncls;
 
     const int p_begin = blockIdx.x * A.px_per_wg, p_end = min(P, p_begin + A.px_per_wg);
-    const int ntile = (p_end > p_begin) ? (p_end - p_begin) / IP_TILE : 0;      // P % 64 == 0, px_per_wg % 512 == 0: whole tiles
-    const int my = (ntile > wave) ? (ntile - wave + IP_WAVES - 1) / IP_WAVES : 0;
-    const int total = my * KS;
+    const int ntile = (p_end > p_begin) ? (p_end - p_begin) / dectile::TILE : 0;      // P % 64 == 0, px_per_wg % 512 == 0: whole tiles
+    const int total = dectile::my_tiles(ntile, wave) * KS;
 
     const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.loc + (size_t)b * C * P), 0, C * P * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.sem + (size_t)b * C * P), 0, C * P * 4, 0x00020000);
@@ -202,51 +169,22 @@ __global__ __launch_bounds__(IP_THREADS, 2) void k_init_pass(const InitPassArgs 
     const __amdgpu_buffer_rsrc_t ers = __builtin_amdgcn_make_buffer_rsrc(A.seg ? A.seg + (size_t)b * A.ncls * P : A.masks, 0,
                                                                          A.seg ? A.ncls * P * 4 : 0, 0x00020000);
 
-    ip_u32x2 L0[8], S0[8], L1[8], S1[8];
+    dectile::u32x2 L0[8], S0[8], L1[8], S1[8];
     int ld_ks = 0, ld_sl = 0, ld_cnt = 0, c_ks = 0, c_sl = 0;
     const int voff = ((g << 3) * P + 2 * li) << 2;
 #define IP_LOAD(LR, SR)                                                                                      \
     do {                                                                                                     \
-        const int soff_ = ((ld_ks << 4) * P + p_begin + (wave + IP_WAVES * ld_sl) * IP_TILE) << 2;           \
+        const int soff_ = ((ld_ks << 4) * P + DECTILE_TILE_P0(p_begin, wave, ld_sl)) << 2;           \
         _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                      \
             LR[e] = __builtin_amdgcn_raw_buffer_load_b64(lrs, voff, soff_ + ((e * P) << 2), 3);              \
             SR[e] = __builtin_amdgcn_raw_buffer_load_b64(srs, voff, soff_ + ((e * P) << 2), 3);              \
         }                                                                                                    \
-        const bool adv_ = (ld_cnt + 1 < total), wrap_ = (ld_ks + 1 == KS);                                   \
-        ld_cnt += adv_ ? 1 : 0;                                                                              \
-        ld_sl += (adv_ && wrap_) ? 1 : 0;                                                                    \
-        ld_ks = adv_ ? (wrap_ ? 0 : ld_ks + 1) : ld_ks;                                                      \
+        DECTILE_ADVANCE_LOAD(ld_ks, ld_sl, ld_cnt, total, KS)                                                \
     } while (0)
 
     if (total > 0) IP_LOAD(L0, S0);   // the first pair is requested before the planes are staged (its latency runs under the staging)
     {   // planes -> LDS (rows >= Np + ncls: zero), bias of the semantic rows
-        const int cpr = C >> 3;
-        // (four iterations' loads in flight before the first LDS store, as in k_decode_mfma: a rolled load -> store loop is one memory
-        // round trip per iteration)
-        const int items = NB * 32 * cpr;
-        for (int i0 = tid; i0 < items; i0 += 4 * IP_THREADS) {
-            half8 vh[4], vl[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = i0 + u * IP_THREADS;
-                const int r = i / cpr, q = i - r * cpr;
-                vh[u] = half8{0, 0, 0, 0, 0, 0, 0, 0};
-                vl[u] = half8{0, 0, 0, 0, 0, 0, 0, 0};
-                if (i < items && r < Ntot) {
-                    vh[u] = *reinterpret_cast<const half8*>(A.kh + (size_t)r * C + q * 8);
-                    vl[u] = *reinterpret_cast<const half8*>(A.kl + (size_t)r * C + q * 8);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = i0 + u * IP_THREADS;
-                if (i < items) {
-                    const int r = i / cpr, q = i - r * cpr;
-                    *reinterpret_cast<half8*>(ldsH + r * LDK + q * 8) = vh[u];
-                    *reinterpret_cast<half8*>(ldsL + r * LDK + q * 8) = vl[u];
-                }
-            }
-        }
+        DECTILE_STAGE_PLANES(NB, ldsH, ldsL, LDK, C, A.kh, A.kl, tid, r_ < Ntot)
         if (tid < NB * 32) kbs[tid] = (A.seg_b && tid >= A.Np && tid < Ntot) ? A.seg_b[tid - A.Np] : 0.f;
         __syncthreads();
     }
@@ -259,65 +197,41 @@ __global__ __launch_bounds__(IP_THREADS, 2) void k_init_pass(const InitPassArgs 
     for (int nb = 0; nb < NB; ++nb) thing_row[nb] = (nb * 32 + li) < A.Np;
     const half8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
 
-#define IP_SPLIT(REG)                                                     \
-    _Pragma("unroll") for (int e = 0; e < 8; ++e) {                       \
-        _Float16 h_, l_;                                                  \
-        const unsigned u0_ = REG[e][0], u1_ = REG[e][1];                  \
-        vkn_split_f16(__uint_as_float(u0_), h_, l_);                      \
-        bh0[e] = h_; bl0[e] = l_;                                         \
-        vkn_split_f16(__uint_as_float(u1_), h_, l_);                      \
-        bh1[e] = h_; bl1[e] = l_;                                         \
-    }
-#define IP_MFMA6(AH, AL, NBI)                                                                      \
-    do {                                                                                           \
-        acc[0][NBI] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, bh0, acc[0][NBI], 0, 0, 0);       \
-        acc[1][NBI] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, bh1, acc[1][NBI], 0, 0, 0);       \
-        acc[0][NBI] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, bl0, acc[0][NBI], 0, 0, 0);       \
-        acc[1][NBI] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, bl1, acc[1][NBI], 0, 0, 0);       \
-        acc[0][NBI] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL, bh0, acc[0][NBI], 0, 0, 0);       \
-        acc[1][NBI] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL, bh1, acc[1][NBI], 0, 0, 0);       \
-    } while (0)
-
 #define IP_COMPUTE(LR, SR)                                                                                         \
     do {                                                                                                           \
         if (c_ks == 0) {                                                                                           \
-            _Pragma("unroll") for (int nb = 0; nb < NB; ++nb)                                                      \
-                _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                   \
-                    const float kb_ = kbs[nb * 32 + vkn_cd_row(r, lane)];                                          \
-                    acc[0][nb][r] = kb_;                                                                           \
-                    acc[1][nb][r] = kb_;                                                                           \
-                }                                                                                                  \
+            DECTILE_BIAS_ACC(acc, NB, kbs, lane)                                                                   \
         }                                                                                                          \
-        const int p0_ = p_begin + (wave + IP_WAVES * c_sl) * IP_TILE;                                              \
+        const int p0_ = DECTILE_TILE_P0(p_begin, wave, c_sl);                                              \
         {   /* x = loc + sem for the pair's 16 channels x 2 pixels */                                              \
             const int soff_ = ((c_ks << 4) * P + p0_) << 2;                                                        \
             _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                        \
-                const ip_u32x2 v_ = {__float_as_uint(__uint_as_float(LR[e][0]) + __uint_as_float(SR[e][0])),       \
+                const dectile::u32x2 v_ = {__float_as_uint(__uint_as_float(LR[e][0]) + __uint_as_float(SR[e][0])),       \
                                      __float_as_uint(__uint_as_float(LR[e][1]) + __uint_as_float(SR[e][1]))};      \
                 __builtin_amdgcn_raw_buffer_store_b64(v_, xrs, voff, soff_ + ((e * P) << 2), 0);                   \
             }                                                                                                      \
         }                                                                                                          \
         const int cb_ = (c_ks << 4) + (g << 3);                                                                    \
         half8 bh0, bl0, bh1, bl1;                                                                                  \
-        IP_SPLIT(LR)                                                                                               \
+        DECTILE_SPLIT_PAIR(LR, bh0, bl0, bh1, bl1)                                                                                              \
         _Pragma("unroll") for (int nb = 0; nb < NBL; ++nb) {                                                       \
             const _Float16* ap_ = ldsH + (nb * 32 + li) * LDK + cb_;                                               \
             half8 ah_ = *reinterpret_cast<const half8*>(ap_);                                                      \
             half8 al_ = *reinterpret_cast<const half8*>(ap_ + NB * 32 * LDK);                                      \
             if (nb >= SLO) { ah_ = thing_row[nb] ? ah_ : hz; al_ = thing_row[nb] ? al_ : hz; }                     \
-            IP_MFMA6(ah_, al_, nb);                                                                                \
+            dectile::mfma6(ah_, al_, bh0, bl0, bh1, bl1, acc[0][nb], acc[1][nb]);                                                                                \
         }                                                                                                          \
-        IP_SPLIT(SR)                                                                                               \
+        DECTILE_SPLIT_PAIR(SR, bh0, bl0, bh1, bl1)                                                                                              \
         _Pragma("unroll") for (int nb = SLO; nb <= SHI; ++nb) {                                                    \
             const _Float16* ap_ = ldsH + (nb * 32 + li) * LDK + cb_;                                               \
             half8 ah_ = *reinterpret_cast<const half8*>(ap_);                                                      \
             half8 al_ = *reinterpret_cast<const half8*>(ap_ + NB * 32 * LDK);                                      \
             ah_ = thing_row[nb] ? hz : ah_; al_ = thing_row[nb] ? hz : al_;                                        \
-            IP_MFMA6(ah_, al_, nb);                                                                                \
+            dectile::mfma6(ah_, al_, bh0, bl0, bh1, bl1, acc[0][nb], acc[1][nb]);                                                                                \
         }                                                                                                          \
         if (++c_ks == KS) {                                                                                        \
             ip_store_tile<NB, SLO>(acc, A, mrs, ers, p0_, li, g, Ntot);                                            \
-            if (A.bits) ip_emit_bits<NB>(acc, A.thr, A.bits + ((size_t)b * (P >> 5) + ((p0_ >> 6) << 1)) * A.npt, A.npt, lane); \
+            if (A.bits) dectile::emit_bits<NB>(acc, A.thr, A.bits + ((size_t)b * (P >> 5) + ((p0_ >> 6) << 1)) * A.npt, A.npt, lane); \
             c_ks = 0;                                                                                              \
             ++c_sl;                                                                                                \
         }                                                                                                          \
@@ -331,8 +245,6 @@ __global__ __launch_bounds__(IP_THREADS, 2) void k_init_pass(const InitPassArgs 
         IP_COMPUTE(L1, S1);
     }
 #undef IP_LOAD
-#undef IP_SPLIT
-#undef IP_MFMA6
 #undef IP_COMPUTE
 }
 
@@ -349,18 +261,15 @@ int vkn_launch_init_pass(const InitPassArgs& a, int B, hipStream_t st) {
     const int kind = vkn_init_pass_supported(a.Np, a.ncls, a.C, a.P);
     if (!kind) return VKN_E_SHAPE;
     InitPassArgs A = a;
-    long long ppx = ((long long)B * a.P + 255) / 256;      // one persistent workgroup per CU over the batch when it is large enough
-    A.px_per_wg = (int)((ppx + 511) / 512 * 512);
-    if (A.px_per_wg < 512) A.px_per_wg = 512;
+    A.px_per_wg = vkn_decode_split(B, a.P, 0).px_per_wg;   // one persistent workgroup per CU over the batch when it is large enough
     const dim3 grid((a.P + A.px_per_wg - 1) / A.px_per_wg, B);
-    const int NB = kind == 1 ? 4 : 1;
-    const size_t lds = (size_t)2 * NB * 32 * (a.C + 8) * sizeof(_Float16) + (size_t)NB * 32 * sizeof(float);
+    const size_t lds = dectile::lds_bytes(kind == 1 ? 4 : 1, a.C);
     if (kind == 1) {
         VKN_ALLOW_FULL_LDS((k_init_pass<4, 3, 3>));
-        hipLaunchKernelGGL((k_init_pass<4, 3, 3>), grid, dim3(IP_THREADS), lds, st, A);
+        hipLaunchKernelGGL((k_init_pass<4, 3, 3>), grid, dim3(dectile::THREADS), lds, st, A);
     } else {
         VKN_ALLOW_FULL_LDS((k_init_pass<1, 0, 0>));
-        hipLaunchKernelGGL((k_init_pass<1, 0, 0>), grid, dim3(IP_THREADS), lds, st, A);
+        hipLaunchKernelGGL((k_init_pass<1, 0, 0>), grid, dim3(dectile::THREADS), lds, st, A);
     }
     VKN_CHECK_LAUNCH();
     return VKN_OK;
