@@ -24,6 +24,7 @@ from .seg_tail import SegLossTail  # noqa: F401
 from .stq_meter import STQMeter  # noqa: F401
 from .vpq_meter import VPQMeter  # noqa: F401
 from .mask_rle import MaskRLE, encode_mask_results  # noqa: F401
+from .mask_ap_meter import MaskAPMeter  # noqa: F401
 from .registry import HEADS, NECKS, TRANSFORMER_LAYER, build_head, build_neck, build_transformer_layer  # noqa: F401
 from . import autograd, losses  # noqa: F401
 from .mask_pseudo_sampler import MaskPseudoSampler  # noqa: F401

@@ -3,8 +3,9 @@
 //
 // The input is row-major, the RLE order column-major (p = x * H + y).  A workgroup owns a STRIP of VKN_RLE_STRIP_COLS = 64 columns of one
 // mask, so that one row of a strip is one 64-bit word:
-//   1. k_rle_pack     reads the input ONCE, in aligned 16-byte pieces whatever W is, and stores the masks as bits [K][strips][H].  Every
-//                     later launch reads those words only: 1/8 of the u8 input, 1/32 of the fp32 input.
+//   1. k_rle_pack     (vkn_maskbits.h, shared with vkn_maskap.hip) reads the input ONCE, in aligned 16-byte pieces whatever W is, and
+//                     stores the masks as bits [K][strips][H].  Every later launch reads those words only: 1/8 of the u8 input, 1/32 of
+//                     the fp32 input.
 //   2. k_rle_count    per strip: thread (segment w of 4, column c of 64) walks its quarter of column c downwards; a transition at (y, x)
 //                     is bit c of bits[y] ^ bits[y-1], row 0 against the LAST row of column x - 1 (the word before the strip's first
 //                     word is the previous strip's last row).  Per strip: the number of transitions and the positions of its last three,
@@ -18,14 +19,15 @@
 // counts[i-2], four positions), and "append" on such states is associative, so one block scan serves transitions and bytes alike.
 #include "../../include/vkn_rle.h"
 #include "vkn_common.h"
+#include "vkn_maskbits.h"
 #include <limits.h>
 
 namespace {
 
-constexpr int RLE_THREADS = 256;
+constexpr int RLE_THREADS = MASKBITS_THREADS;
 constexpr int RLE_SEGS = RLE_THREADS / VKN_RLE_STRIP_COLS;      // row segments of a strip: one wave each
 constexpr int RLE_CHUNK = 256;                                  // rows of its segment that a wave holds in LDS at a time
-static_assert(VKN_RLE_STRIP_COLS == 64 && RLE_SEGS == 4, "a strip row is one 64-bit word, a wave walks one row segment");
+static_assert(VKN_RLE_STRIP_COLS == 64 && VKN_RLE_STRIP_COLS == MASKBITS_STRIP_COLS && RLE_SEGS == 4, "a strip row is one 64-bit word, a wave walks one row segment");
 
 // What is known of a sequence of transitions: how many, and the positions of the last three (0 where there are fewer: p[-1] = 0 is the
 // format's start, and the others are read only behind three real transitions).
@@ -92,57 +94,6 @@ __device__ __forceinline__ St block_scan(St* sh, int e, const St& v, const St& s
     total = st_cat(seed, sh[RLE_THREADS - 1]);
     __syncthreads();
     return excl;
-}
-
-// ------------------------------------------------------------------------------------------------------------------------ pack
-template <typename T>
-__device__ __forceinline__ bool rle_set(T v, float thr);
-template <>
-__device__ __forceinline__ bool rle_set<unsigned char>(unsigned char v, float) { return v != 0; }
-template <>
-__device__ __forceinline__ bool rle_set<float>(float v, float thr) { return v > thr; }
-
-// grid (strips, K).  LPR lanes share a row of the strip: lane j takes the j-th ALIGNED 16-byte piece that the row's 64 elements touch
-// (64 / EPC + 1 pieces at most) and keeps the elements that belong to the row; the row's word is the OR over its lanes.  A piece that
-// would end behind the tensor is read element by element.
-template <typename T, int LPR>
-__global__ __launch_bounds__(RLE_THREADS) void k_rle_pack(const T* __restrict__ in, float thr, unsigned long long* __restrict__ bits, int H, int W,
-                                                          long long total) {
-    constexpr int EPC = 16 / (int)sizeof(T), RPI = RLE_THREADS / LPR;
-    static_assert(VKN_RLE_STRIP_COLS / EPC + 1 <= LPR && LPR <= 32, "the lanes of a row cover its pieces and stay inside half a wave");
-    const int s = blockIdx.x, k = blockIdx.y;
-    const int x0 = s * VKN_RLE_STRIP_COLS, sw = min(VKN_RLE_STRIP_COLS, W - x0);
-    const int j = threadIdx.x % LPR, r = threadIdx.x / LPR;
-    unsigned long long* out = bits + ((size_t)k * gridDim.x + s) * (size_t)H;
-    const long long mbase = (long long)k * H * W + x0;
-    for (long long yb = 0; yb < H; yb += RPI) {
-        const long long y = yb + r;
-        unsigned long long word = 0;
-        if (y < H) {
-            const long long e0 = mbase + y * W;               // the row's first element in the strip
-            const long long c0 = (e0 / EPC + j) * EPC;        // this lane's piece
-            if (c0 < e0 + sw) {
-                union {
-                    uint4 q;
-                    T v[EPC];
-                } u;
-                if (c0 + EPC <= total) {
-                    u.q = *reinterpret_cast<const uint4*>(in + c0);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < EPC; ++e) u.v[e] = c0 + e < total ? in[c0 + e] : (T)0;
-                }
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) {
-                    const long long col = c0 + e - e0;
-                    if (col >= 0 && col < sw && rle_set<T>(u.v[e], thr)) word |= 1ull << col;
-                }
-            }
-        }
-#pragma unroll
-        for (int d = 1; d < LPR; d <<= 1) word |= __shfl_xor(word, d);
-        if (j == 0 && y < H) out[y] = word;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ walks
@@ -416,7 +367,7 @@ inline RleLayout rle_layout(int K, int H, int W) {
     return l;
 }
 
-template <typename T, int LPR>
+template <typename T>
 int rle_encode(const T* in, float thr, int K, int H, int W, int* records, unsigned* runs, int cap_runs, unsigned char* bytes, int cap_bytes,
                unsigned* status, void* ws, size_t ws_bytes, void* stream) {
     if (!in || !records || !runs || !bytes || !status || !ws || K < 0 || H < 0 || W < 0 || cap_runs < 0 || cap_bytes < 0) return VKN_E_ARG;
@@ -439,8 +390,7 @@ int rle_encode(const T* in, float thr, int K, int H, int W, int* records, unsign
     unsigned* tot = reinterpret_cast<unsigned*>(base + l.tot);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 strips((unsigned)l.NS, (unsigned)K), block(RLE_THREADS);
-    hipLaunchKernelGGL((k_rle_pack<T, LPR>), strips, block, 0, st, in, thr, bits, H, W, (long long)K * H * W);
-    VKN_CHECK_LAUNCH();
+    if (!maskbits_pack<T>(in, thr, K, H, W, bits, st)) return VKN_E_LAUNCH;
     hipLaunchKernelGGL(k_rle_count, strips, block, 0, st, bits, sum, stat, H, W);
     VKN_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_rle_scan_mask<0>, dim3(K), block, 0, st, sum, state, stat, sbytes, sboff, tot, records, l.NS);
@@ -469,12 +419,12 @@ size_t vkn_rle_workspace_bytes(int K, int H, int W) {
 
 int vkn_rle_encode_u8(const unsigned char* masks, int K, int H, int W, int* records, unsigned* runs, int cap_runs, unsigned char* bytes,
                       int cap_bytes, unsigned* status, void* ws, size_t ws_bytes, void* stream) {
-    return rle_encode<unsigned char, 8>(masks, 0.f, K, H, W, records, runs, cap_runs, bytes, cap_bytes, status, ws, ws_bytes, stream);
+    return rle_encode<unsigned char>(masks, 0.f, K, H, W, records, runs, cap_runs, bytes, cap_bytes, status, ws, ws_bytes, stream);
 }
 
 int vkn_rle_encode_f32(const float* logits, float thr, int K, int H, int W, int* records, unsigned* runs, int cap_runs, unsigned char* bytes,
                        int cap_bytes, unsigned* status, void* ws, size_t ws_bytes, void* stream) {
-    return rle_encode<float, 32>(logits, thr, K, H, W, records, runs, cap_runs, bytes, cap_bytes, status, ws, ws_bytes, stream);
+    return rle_encode<float>(logits, thr, K, H, W, records, runs, cap_runs, bytes, cap_bytes, status, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

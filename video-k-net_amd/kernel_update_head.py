@@ -608,6 +608,12 @@ class KernelUpdateHead(nn.Module):
             segm_result[det_labels[idx]].append(rle)
         return bbox_result, segm_result
 
+    def get_seg_masks_device(self, masks_per_img, labels_per_img, scores_per_img, test_cfg, img_meta):
+        """`get_seg_masks` up to the threshold, with nothing copied to the host: -> (masks bool [K,H,W], labels, scores) on the masks'
+        device, what `mask_ap_meter.MaskAPMeter.update` takes as dt_masks, dt_labels, dt_scores."""
+        seg_masks = self.rescale_masks(masks_per_img, img_meta) > self._meta(test_cfg, 'mask_thr')
+        return seg_masks, labels_per_img, scores_per_img
+
     def segm2result(self, mask_preds, det_labels, cls_scores):
         """One D2H copy of the K boolean masks; per-class lists exactly as the reference builds them (:468-481)."""
         import numpy as np

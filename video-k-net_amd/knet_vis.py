@@ -179,6 +179,8 @@ class KernelUpdateHeadVideo(_QueryMerge, KernelUpdateHead):
 
     # the VIS head's instance results as COCO RLE dicts: the image head's method (rescale as above, threshold + encoding on the device)
     get_seg_masks_rle = KernelUpdateHead.get_seg_masks_rle
+    # ... and as device tensors for the mask-AP meter: the image head's method
+    get_seg_masks_device = KernelUpdateHead.get_seg_masks_device
 
 
 KernelUpdateHead.get_seg_masks_tracking = KernelUpdateHeadVideo.get_seg_masks_tracking   # the per-frame head has it too (:484)

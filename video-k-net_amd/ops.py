@@ -1836,3 +1836,117 @@ def rle_encode(masks, records, runs, pool, status, ws, thr=None):
             check(L.vkn_rle_encode_u8(_ptr(src), *tail))
         else:
             check(L.vkn_rle_encode_f32(_ptr(src), float(thr), *tail))
+
+
+# ---- COCO mask AP (include/vkn_maskap.h): exact overlap tables, and the per-image matching into a caller-owned state
+def mask_overlap_workspace_bytes(K, G, H, W):
+    """vkn_mask_overlap_workspace_bytes: bytes of one call's workspace; 0 outside the envelope of include/vkn_maskap.h and for K = G = 0."""
+    return int(_lib.lib().vkn_mask_overlap_workspace_bytes(int(K), int(G), int(H), int(W)))
+
+
+def mask_overlap(dt, gt, thr=None, out=None):
+    """Pairwise overlap of K detections and G ground truths (vkn_mask_overlap_u8 / _f32: two packs and one overlap launch, no
+    synchronisation).  dt: bool or uint8 [K,H,W] (nonzero = set), or float32 [K,H,W] with `thr` (set iff v > thr); gt: bool or uint8
+    [G,H,W].  K = 0 and G = 0 are valid.  -> (inter int64 [K,G], area_dt int64 [K], area_gt int64 [G]) on the masks' device; with
+    `out` (such a triple) the call ADDS into it and returns it: per frame of a video, that yields tube overlaps."""
+    for t, name in ((dt, 'dt'), (gt, 'gt')):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.VknLibraryError(f'mask_overlap: {name}: expected a CUDA/HIP tensor — the MI355X path has no CPU fallback')
+    if dt.dtype == torch.float32:
+        if thr is None:
+            raise ValueError('mask_overlap: float32 logits need `thr`')
+        d = _req(dt, 'dt')
+    else:
+        if thr is not None:
+            raise ValueError('mask_overlap: `thr` goes with float32 logits only')
+        d = _req_bytes(dt, 'dt')
+    g = _req_bytes(gt, 'gt')
+    if d.dim() != 3 or g.dim() != 3 or d.shape[1:] != g.shape[1:] or d.device != g.device:
+        raise ValueError(f'mask_overlap: dt [K,H,W] and gt [G,H,W] of one size on one device, got {tuple(d.shape)} and {tuple(g.shape)}')
+    d, g = (t.clone() if t.data_ptr() % 16 else t for t in (d, g))
+    K, H, W = (int(s) for s in d.shape)
+    G = int(g.shape[0])
+    elem = 4 if thr is not None else 1
+    need = mask_overlap_workspace_bytes(K, G, H, W)
+    if (K + G and not need) or K * H * W * elem >= 2 ** 31:
+        raise _lib.VknError(-2, f'mask_overlap: {K} x {G} masks of {H} x {W} are outside the envelope of include/vkn_maskap.h '
+                                f'(K, G <= {_lib.MASKAP["VKN_MASKAP_MAX_MASKS"]}, H * W < 2^31, max(K, G) * H * W * element size < 2^31)')
+    if out is None:
+        flat = torch.zeros((K * G + K + G + 6,), dtype=torch.int64, device=d.device)        # one fill; each table on a 16-byte boundary
+        a, b = (K * G + 1) // 2 * 2, (K * G + 1) // 2 * 2 + (K + 1) // 2 * 2
+        out = flat[:K * G].view(K, G), flat[a:a + K], flat[b:b + G]
+    inter, area_dt, area_gt = (_req_plain(t, n, torch.int64) for t, n in zip(out, ('inter', 'area_dt', 'area_gt')))
+    if tuple(inter.shape) != (K, G) or tuple(area_dt.shape) != (K,) or tuple(area_gt.shape) != (G,) or any(t.device != d.device for t in (inter, area_dt, area_gt)):
+        raise ValueError(f'mask_overlap: out = (int64 [{K},{G}], int64 [{K}], int64 [{G}]) on the masks\' device')
+    if K + G == 0:
+        return inter, area_dt, area_gt
+    ws = _workspace(need, d.device, scratch=True)[:need]
+    L = _lib.lib()
+    opt = lambda t: _ptr(t if t.numel() else None)          # noqa: E731  (an empty side travels as NULL)
+    tail = (opt(g), K, G, H, W, opt(inter), opt(area_dt), opt(area_gt), _ptr(ws), need, _stream())
+    with torch.cuda.device(d.device):
+        if thr is None:
+            check(L.vkn_mask_overlap_u8(opt(d), *tail))
+        else:
+            check(L.vkn_mask_overlap_f32(opt(d), float(thr), *tail))
+    return inter, area_dt, area_gt
+
+
+def mask_ap_cfg(num_classes, iou_thrs, area_ranges, max_det, cap_records):
+    """The `VknMaskApCfg` of a meter; raises VknError (VKN_E_SHAPE) outside the envelope of include/vkn_maskap.h."""
+    C = _lib.MASKAP
+    thrs, areas = [float(t) for t in iou_thrs], [(float(lo), float(hi)) for lo, hi in area_ranges]
+    if not 1 <= len(thrs) <= C['VKN_MASKAP_MAX_THRS'] or not 1 <= len(areas) <= C['VKN_MASKAP_MAX_AREAS']:
+        raise _lib.VknError(-2, f'mask_ap_cfg: 1 to {C["VKN_MASKAP_MAX_THRS"]} IoU thresholds and 1 to {C["VKN_MASKAP_MAX_AREAS"]} area ranges, '
+                                f'got {len(thrs)} and {len(areas)}')
+    cfg = _lib.VknMaskApCfg()
+    cfg.iou_thrs[:len(thrs)] = thrs
+    cfg.area_lo[:len(areas)], cfg.area_hi[:len(areas)] = [a[0] for a in areas], [a[1] for a in areas]
+    cfg.num_classes, cfg.T, cfg.A, cfg.max_det, cfg.cap_records = int(num_classes), len(thrs), len(areas), int(max_det), int(cap_records)
+    if not _lib.lib().vkn_mask_ap_state_bytes(ctypes.byref(cfg)):
+        raise _lib.VknError(-2, f'mask_ap_cfg: outside the envelope of include/vkn_maskap.h (num_classes 1..{C["VKN_MASKAP_MAX_CLASSES"]}, '
+                                f'max_det 1..{C["VKN_MASKAP_MAX_MASKS"]}, capacity 1..2^24, no NaN)')
+    return cfg
+
+
+def mask_ap_layout(cfg):
+    """(state bytes, the three byte offsets: header, npig, log)"""
+    off = (ctypes.c_size_t * 3)()
+    check(_lib.lib().vkn_mask_ap_state_layout(ctypes.byref(cfg), off))
+    return int(_lib.lib().vkn_mask_ap_state_bytes(ctypes.byref(cfg))), [int(o) for o in off]
+
+
+def mask_ap_state(cfg, device):
+    """A freshly reset state: uint8 [vkn_mask_ap_state_bytes] on `device`."""
+    state = torch.empty((mask_ap_layout(cfg)[0],), dtype=torch.uint8, device=device)
+    return mask_ap_reset(cfg, state)
+
+
+def mask_ap_reset(cfg, state):
+    """Empty the state (vkn_mask_ap_reset, one fill); returns it."""
+    with torch.cuda.device(state.device):
+        check(_lib.lib().vkn_mask_ap_reset(ctypes.byref(cfg), _ptr(state), state.numel(), _stream()))
+    return state
+
+
+def mask_ap_match(cfg, state, tables, scores, dt_labels, gt_labels, gt_crowd, gt_area=None, image_seq=0, match_gt=None):
+    """Match one image into `state` (vkn_mask_ap_match, three launches, no synchronisation).  tables: `mask_overlap`'s triple; scores
+    float32 [K], dt_labels int32 [K], gt_labels int32 [G], gt_crowd uint8 [G], gt_area float64 [G] or None (the pixel count),
+    match_gt int32 [A,T,K] or None: CUDA tensors on the state's device."""
+    inter, area_dt, area_gt = (_req_plain(t, n, torch.int64) for t, n in zip(tables, ('inter', 'area_dt', 'area_gt')))
+    K, G = int(area_dt.numel()), int(area_gt.numel())
+    scores = _req_plain(scores, 'scores', torch.float32)
+    dt_labels, gt_labels = _req_plain(dt_labels, 'dt_labels', torch.int32), _req_plain(gt_labels, 'gt_labels', torch.int32)
+    gt_crowd = _req_bytes(gt_crowd, 'gt_crowd')
+    gt_area = _req_plain(gt_area, 'gt_area', torch.float64) if gt_area is not None else None
+    match_gt = _req_plain(match_gt, 'match_gt', torch.int32) if match_gt is not None else None
+    if (inter.numel() != K * G or scores.numel() != K or dt_labels.numel() != K or gt_labels.numel() != G or gt_crowd.numel() != G
+            or (gt_area is not None and gt_area.numel() != G) or (match_gt is not None and match_gt.numel() != cfg.A * cfg.T * K)):
+        raise ValueError(f'mask_ap_match: tables of {K} detections and {G} ground truths need scores, dt_labels [{K}], gt_labels, gt_crowd, '
+                         f'gt_area [{G}] and match_gt [{cfg.A},{cfg.T},{K}]')
+    if any(t is not None and t.device != state.device for t in (inter, area_dt, area_gt, scores, dt_labels, gt_labels, gt_crowd, gt_area, match_gt)):
+        raise ValueError('mask_ap_match: everything on the state\'s device')
+    opt = lambda t: _ptr(t if t is not None and t.numel() else None)          # noqa: E731
+    with torch.cuda.device(state.device):
+        check(_lib.lib().vkn_mask_ap_match(ctypes.byref(cfg), _ptr(state), state.numel(), opt(inter), opt(area_dt), opt(area_gt), opt(scores),
+                                           opt(dt_labels), opt(gt_labels), opt(gt_crowd), opt(gt_area), K, G, int(image_seq), opt(match_gt), _stream()))
