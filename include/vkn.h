@@ -537,6 +537,19 @@ size_t vkn_panoptic_workspace_bytes(const VknPanopticCfg* cfg, int B, int N);
  *           bbox int32 [B][K][4] or NULL: (xmin, ymin, xmax, ymax) of `panoptic_seg == id` for accepted entries, else (-1,-1,10,10)
  *           = `tensor_mask2box` (unitrack/utils/mask.py:80-90) on the segment masks, what the video detector hands its tracker
  *           (knet/video/knet_quansi_dense_embed_fc_joint_train.py:541-584).
+ *      Tie rules (torch leaves all three unspecified; tests/test_gpu_pan_joint_pins.py holds the library to them):
+ *        selection   things: the max_per_img best of cls_prob[:num_proposals, :num_thing_classes] by (score descending, flat index
+ *                    proposal * num_thing_classes + class ascending) — a mask row whose scores in two classes are bit-equal is listed
+ *                    lower class first; stuff: by (diagonal score descending, stuff row ascending);
+ *        arg-max     the FIRST maximum of score * prob in entry order wins a pixel: of two entries with bit-equal products (the same
+ *                    mask row selected twice, identical planes with equal scores) the earlier entry takes every pixel, the later
+ *                    one keeps area 0 and is rejected;
+ *        merge order entries by (score descending, entry index ascending), things and stuff together; segment ids count accepted
+ *                    entries only, in that order.
+ *      Accept / reject, per entry in merge order: a thing with score < instance_score_thr (fp32 compare) is rejected; else the entry
+ *      is accepted iff area > 0, orig > 0 and not ((double)area / orig < overlap_thr).  A rejected winner's pixels are 0 in the map.
+ *      Limits: any K >= 1.  A geometry whose one-tile footprint does not fit LDS (extreme down-scaling) returns VKN_E_SHAPE with no
+ *      output written.
  *      Width limit: Wm <= 4096, else VKN_E_SHAPE.  The footprint-bounds pass keeps a strip of column (min, max) rows of the full
  *      logit width in LDS; the strip is 8 tile rows high up to Wm = 512 and shrinks to 1 tile row at Wm = 4096.  (`get_panoptic`
  *      passes up-scaled masks with up = 1: Wm = 624 for a KITTI-STEP frame, 1024 for a Cityscapes frame.) */

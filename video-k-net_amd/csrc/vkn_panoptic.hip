@@ -680,6 +680,7 @@ int vkn_launch_panoptic_joint(const VknPanopticCfg* c, const float* cls, const f
     int KC = (int)(budget / ln_bytes);
     if (KC >= K) KC = K;
     KC = KC / PAN_KB * PAN_KB;
+    if (KC < PAN_KB) KC = PAN_KB;  // K < PAN_KB: a chunk of 0 would never advance k_pan_argmax's chunk loop (PAN_KB footprints fit: checked above)
     lds += (size_t)KC * ln_bytes;
     dim3 grid((c->Wo + PAN_TW - 1) / PAN_TW, (c->Ho + PAN_TH - 1) / PAN_TH, B);
     // (tried: an XCD-aware unit order that assembles every 128-byte line of `bounds` in one L2 — 168 us against 160: not the limit)
