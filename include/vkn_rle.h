@@ -22,8 +22,9 @@
  *
  *   area = the number of set pixels; bbox = [x0, y0, x1 - x0 + 1, y1 - y0 + 1] over the set pixels, [0, 0, 0, 0] for an empty mask.
  *
- * Not built: the rescale of the low-resolution logits (two bilinear resamplings with a crop between them: it stays the caller's),
- * polygon or uncompressed input, decoding, merging and IoU on RLEs.
+ * The rescale of the low-resolution logits (two bilinear resamplings with a crop between them) is vkn_instmask.h's: it writes the masks
+ * as bits, and its vkn_bits_rle_encode is this encoder on such bits, without the pack pass.
+ * Not built: polygon or uncompressed input, decoding, merging and IoU on RLEs.
  */
 #ifndef VKN_RLE_H
 #define VKN_RLE_H

@@ -19,6 +19,7 @@
 // threshold, k_ap_end advances the record count: the hand-offs (the count that the first two read and the third writes) are kernel
 // boundaries.  The work is small and sequential per threshold, like the device LSAP.
 #include "../../include/vkn_maskap.h"
+#include "../../include/vkn_instmask.h"   // vkn_bits_mask_overlap: the overlap with the detections already as bits
 #include "vkn_common.h"
 #include "vkn_maskbits.h"
 
@@ -121,36 +122,46 @@ struct OverlapLayout {
     size_t dbits, gbits, bytes;
     long long NS;
 };
-inline OverlapLayout overlap_layout(int K, int G, int H, int W) {
+// own_dt: the workspace holds the detections as bits too (the u8 / f32 entries); false: the caller hands them in (vkn_bits_mask_overlap)
+inline OverlapLayout overlap_layout(int K, int G, int H, int W, bool own_dt = true) {
     OverlapLayout l;
     l.NS = maskbits_strips(W);
     l.dbits = 0;
-    l.gbits = up16((size_t)K * (size_t)l.NS * (size_t)H * 8);
+    l.gbits = own_dt ? up16((size_t)K * (size_t)l.NS * (size_t)H * 8) : 0;
     l.bytes = l.gbits + up16((size_t)G * (size_t)l.NS * (size_t)H * 8);
     return l;
 }
 
+// T: unsigned char / float detections that the call packs into its workspace, or u64: the detections as bits [K][NS][H]
 template <typename T>
 int mask_overlap(const T* dt, float thr, const unsigned char* gt, int K, int G, int H, int W, long long* inter, long long* area_dt, long long* area_gt,
                  void* ws, size_t ws_bytes, void* stream) {
+    constexpr bool BITS = sizeof(T) == 8;
     if (K < 0 || G < 0 || H < 0 || W < 0) return VKN_E_ARG;
-    if ((K > 0 && (!dt || !area_dt)) || (G > 0 && (!gt || !area_gt)) || (K > 0 && G > 0 && !inter) || (K + G > 0 && !ws)) return VKN_E_ARG;
-    if (!overlap_shape_ok(K, G, H, W, (int)sizeof(T))) return VKN_E_SHAPE;
-    const OverlapLayout l = overlap_layout(K, G, H, W);
+    const bool need_ws = BITS ? G > 0 : K + G > 0;      // the sides that the call packs
+    if ((K > 0 && (!dt || !area_dt)) || (G > 0 && (!gt || !area_gt)) || (K > 0 && G > 0 && !inter) || (need_ws && !ws)) return VKN_E_ARG;
+    if (!overlap_shape_ok(K, G, H, W, BITS ? 1 : (int)sizeof(T))) return VKN_E_SHAPE;
+    const OverlapLayout l = overlap_layout(K, G, H, W, !BITS);
     if (ws_bytes != l.bytes) return VKN_E_WORKSPACE;
     const bool both = K > 0 && G > 0;
     if ((K > 0 && (!vkn_aligned(dt, 16) || !vkn_aligned(area_dt, 16))) || (G > 0 && (!vkn_aligned(gt, 16) || !vkn_aligned(area_gt, 16))) ||
-        (both && !vkn_aligned(inter, 16)) || (K + G > 0 && !vkn_aligned(ws, 16)))
+        (both && !vkn_aligned(inter, 16)) || (need_ws && !vkn_aligned(ws, 16)))
         return VKN_E_ALIGN;
     if ((K > 0 && (!vkn_on_device(dt) || !vkn_on_device(area_dt))) || (G > 0 && (!vkn_on_device(gt) || !vkn_on_device(area_gt))) ||
-        (both && !vkn_on_device(inter)) || (K + G > 0 && !vkn_on_device(ws)))
+        (both && !vkn_on_device(inter)) || (need_ws && !vkn_on_device(ws)))
         return VKN_E_ARG;
     if (K + G == 0) return VKN_OK;
     char* base = static_cast<char*>(ws);
-    u64* dbits = reinterpret_cast<u64*>(base + l.dbits);
-    u64* gbits = reinterpret_cast<u64*>(base + l.gbits);
+    u64* gbits = reinterpret_cast<u64*>(base + l.gbits);      // (never read when G = 0)
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (K > 0 && !maskbits_pack<T>(dt, thr, K, H, W, dbits, st)) return VKN_E_LAUNCH;
+    const u64* dbits;
+    if constexpr (BITS) {
+        dbits = dt;
+    } else {
+        u64* packed = reinterpret_cast<u64*>(base + l.dbits);
+        if (K > 0 && !maskbits_pack<T>(dt, thr, K, H, W, packed, st)) return VKN_E_LAUNCH;
+        dbits = packed;
+    }
     if (G > 0 && !maskbits_pack<unsigned char>(gt, 0.f, G, H, W, gbits, st)) return VKN_E_LAUNCH;
     const long long runs = ((long long)H + MO_RUN - 1) / MO_RUN;
     const dim3 grid((unsigned)(l.NS * runs), (unsigned)(K > 0 ? (K + MO_DT - 1) / MO_DT : 1));
@@ -429,6 +440,16 @@ int vkn_mask_ap_match(const VknMaskApCfg* cfg, void* state, size_t state_bytes, 
     hipLaunchKernelGGL(k_ap_end, dim3(1), dim3(1), 0, st, *cfg, a);
     VKN_CHECK_LAUNCH();
     return VKN_OK;
+}
+
+size_t vkn_bits_mask_overlap_workspace_bytes(int K, int G, int H, int W) {
+    if (!overlap_shape_ok(K, G, H, W, 1)) return 0;
+    return overlap_layout(K, G, H, W, false).bytes;
+}
+
+int vkn_bits_mask_overlap(const long long* dt_bits, const unsigned char* gt, int K, int G, int H, int W, long long* inter, long long* area_dt,
+                          long long* area_gt, void* ws, size_t ws_bytes, void* stream) {
+    return mask_overlap<u64>(reinterpret_cast<const u64*>(dt_bits), 0.f, gt, K, G, H, W, inter, area_dt, area_gt, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

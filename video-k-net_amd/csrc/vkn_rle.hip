@@ -18,6 +18,7 @@
 // the transitions before its own is a small state (how many, and the positions of the last three: run i's byte code needs counts[i] and
 // counts[i-2], four positions), and "append" on such states is associative, so one block scan serves transitions and bytes alike.
 #include "../../include/vkn_rle.h"
+#include "../../include/vkn_instmask.h"   // vkn_bits_rle_encode: this encoder on bits that the caller already holds
 #include "vkn_common.h"
 #include "vkn_maskbits.h"
 #include <limits.h>
@@ -351,12 +352,13 @@ inline bool rle_shape_ok(int K, int H, int W, int elem) {
     return hw < (1ll << 31) && hw * K * elem < (1ll << 31);
 }
 
-inline RleLayout rle_layout(int K, int H, int W) {
+// own_bits: the workspace holds the masks as bits (the u8 / f32 entries); false: the caller hands the bits in (vkn_bits_rle_encode)
+inline RleLayout rle_layout(int K, int H, int W, bool own_bits = true) {
     RleLayout l;
     l.NS = ((long long)W + VKN_RLE_STRIP_COLS - 1) / VKN_RLE_STRIP_COLS;
     const size_t strips = (size_t)K * (size_t)l.NS;
     size_t at = 0;
-    l.bits = at, at += up16(strips * (size_t)H * 8);
+    l.bits = at, at += own_bits ? up16(strips * (size_t)H * 8) : 0;
     l.sum = at, at += strips * sizeof(St);
     l.state = at, at += strips * sizeof(St);
     l.stat = at, at += strips * sizeof(RleStat);
@@ -367,30 +369,17 @@ inline RleLayout rle_layout(int K, int H, int W) {
     return l;
 }
 
-template <typename T>
-int rle_encode(const T* in, float thr, int K, int H, int W, int* records, unsigned* runs, int cap_runs, unsigned char* bytes, int cap_bytes,
-               unsigned* status, void* ws, size_t ws_bytes, void* stream) {
-    if (!in || !records || !runs || !bytes || !status || !ws || K < 0 || H < 0 || W < 0 || cap_runs < 0 || cap_bytes < 0) return VKN_E_ARG;
-    if (!rle_shape_ok(K, H, W, (int)sizeof(T))) return VKN_E_SHAPE;
-    const RleLayout l = rle_layout(K, H, W);
-    if (ws_bytes != l.bytes) return VKN_E_WORKSPACE;
-    if (!vkn_aligned(in, 16) || !vkn_aligned(records, 16) || !vkn_aligned(runs, 16) || !vkn_aligned(bytes, 16) || !vkn_aligned(ws, 16) ||
-        !vkn_aligned(status, 4))
-        return VKN_E_ALIGN;
-    if (!vkn_on_device(in) || !vkn_on_device(records) || !vkn_on_device(runs) || !vkn_on_device(bytes) || !vkn_on_device(status) ||
-        !vkn_on_device(ws))
-        return VKN_E_ARG;
+// the seven launches behind the pack: `bits` [K][NS][H] -> records, pools, status
+int rle_run(const unsigned long long* bits, const RleLayout& l, int K, int H, int W, int* records, unsigned* runs, int cap_runs, unsigned char* bytes,
+            int cap_bytes, unsigned* status, void* ws, hipStream_t st) {
     char* base = static_cast<char*>(ws);
-    auto* bits = reinterpret_cast<unsigned long long*>(base + l.bits);
     St* sum = reinterpret_cast<St*>(base + l.sum);
     St* state = reinterpret_cast<St*>(base + l.state);
     RleStat* stat = reinterpret_cast<RleStat*>(base + l.stat);
     unsigned* sbytes = reinterpret_cast<unsigned*>(base + l.sbytes);
     unsigned* sboff = reinterpret_cast<unsigned*>(base + l.sboff);
     unsigned* tot = reinterpret_cast<unsigned*>(base + l.tot);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 strips((unsigned)l.NS, (unsigned)K), block(RLE_THREADS);
-    if (!maskbits_pack<T>(in, thr, K, H, W, bits, st)) return VKN_E_LAUNCH;
     hipLaunchKernelGGL(k_rle_count, strips, block, 0, st, bits, sum, stat, H, W);
     VKN_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_rle_scan_mask<0>, dim3(K), block, 0, st, sum, state, stat, sbytes, sboff, tot, records, l.NS);
@@ -406,6 +395,31 @@ int rle_encode(const T* in, float thr, int K, int H, int W, int* records, unsign
     hipLaunchKernelGGL(k_rle_emit, strips, block, 0, st, bits, state, sboff, records, runs, (unsigned)cap_runs, bytes, (unsigned)cap_bytes, H, W);
     VKN_CHECK_LAUNCH();
     return VKN_OK;
+}
+
+// T: unsigned char / float masks that the call packs into its workspace, or unsigned long long: the bits themselves
+template <typename T>
+int rle_encode(const T* in, float thr, int K, int H, int W, int* records, unsigned* runs, int cap_runs, unsigned char* bytes, int cap_bytes,
+               unsigned* status, void* ws, size_t ws_bytes, void* stream) {
+    constexpr bool BITS = sizeof(T) == 8;
+    if (!in || !records || !runs || !bytes || !status || !ws || K < 0 || H < 0 || W < 0 || cap_runs < 0 || cap_bytes < 0) return VKN_E_ARG;
+    if (!rle_shape_ok(K, H, W, BITS ? 1 : (int)sizeof(T))) return VKN_E_SHAPE;
+    const RleLayout l = rle_layout(K, H, W, !BITS);
+    if (ws_bytes != l.bytes) return VKN_E_WORKSPACE;
+    if (!vkn_aligned(in, 16) || !vkn_aligned(records, 16) || !vkn_aligned(runs, 16) || !vkn_aligned(bytes, 16) || !vkn_aligned(ws, 16) ||
+        !vkn_aligned(status, 4))
+        return VKN_E_ALIGN;
+    if (!vkn_on_device(in) || !vkn_on_device(records) || !vkn_on_device(runs) || !vkn_on_device(bytes) || !vkn_on_device(status) ||
+        !vkn_on_device(ws))
+        return VKN_E_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if constexpr (BITS) {
+        return rle_run(in, l, K, H, W, records, runs, cap_runs, bytes, cap_bytes, status, ws, st);
+    } else {
+        auto* bits = reinterpret_cast<unsigned long long*>(static_cast<char*>(ws) + l.bits);
+        if (!maskbits_pack<T>(in, thr, K, H, W, bits, st)) return VKN_E_LAUNCH;
+        return rle_run(bits, l, K, H, W, records, runs, cap_runs, bytes, cap_bytes, status, ws, st);
+    }
 }
 
 }  // namespace
@@ -425,6 +439,17 @@ int vkn_rle_encode_u8(const unsigned char* masks, int K, int H, int W, int* reco
 int vkn_rle_encode_f32(const float* logits, float thr, int K, int H, int W, int* records, unsigned* runs, int cap_runs, unsigned char* bytes,
                        int cap_bytes, unsigned* status, void* ws, size_t ws_bytes, void* stream) {
     return rle_encode<float>(logits, thr, K, H, W, records, runs, cap_runs, bytes, cap_bytes, status, ws, ws_bytes, stream);
+}
+
+size_t vkn_bits_rle_workspace_bytes(int K, int H, int W) {
+    if (!rle_shape_ok(K, H, W, 1)) return 0;
+    return rle_layout(K, H, W, false).bytes;
+}
+
+int vkn_bits_rle_encode(const long long* bits, int K, int H, int W, int* records, unsigned* runs, int cap_runs, unsigned char* bytes,
+                        int cap_bytes, unsigned* status, void* ws, size_t ws_bytes, void* stream) {
+    return rle_encode<unsigned long long>(reinterpret_cast<const unsigned long long*>(bits), 0.f, K, H, W, records, runs, cap_runs, bytes, cap_bytes,
+                                          status, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

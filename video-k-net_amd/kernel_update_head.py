@@ -596,9 +596,23 @@ class KernelUpdateHead(nn.Module):
         """`get_seg_masks` with the masks as COCO RLE dicts: what `encode_mask_results` (external/test.py:55-70) makes of its result,
         without the K full-resolution masks ever reaching the host.  The rescale is `rescale_masks` as it is; the threshold and the
         encoding are one device call on its fp32 output (`mask_rle.MaskRLE`, include/vkn_rle.h: set iff v > mask_thr, torch's `>`)."""
+        return self._seg_masks_rle(masks_per_img, labels_per_img, scores_per_img, test_cfg, img_meta, False)
+
+    def get_seg_masks_rle_fused(self, masks_per_img, labels_per_img, scores_per_img, test_cfg, img_meta):
+        """`get_seg_masks_rle` with the fused rescale: the masks come as bits straight from the logits (`MaskRLE.encode_logits`,
+        include/vkn_instmask.h) and no full-resolution fp32 map is formed.  Pixels whose probability lies within 1e-4 of mask_thr may
+        differ from `get_seg_masks_rle`; everything else is its result bit for bit.  (A method of its own, not a keyword of
+        `get_seg_masks_rle`: that method's parameter list is `get_seg_masks`'s.)"""
+        return self._seg_masks_rle(masks_per_img, labels_per_img, scores_per_img, test_cfg, img_meta, True)
+
+    def _seg_masks_rle(self, masks_per_img, labels_per_img, scores_per_img, test_cfg, img_meta, fused_rescale):
         import numpy as np
         from .mask_rle import default_encoder
-        rles = default_encoder()(self.rescale_masks(masks_per_img, img_meta).float(), thr=float(self._meta(test_cfg, 'mask_thr')))
+        thr = float(self._meta(test_cfg, 'mask_thr'))
+        if fused_rescale:
+            rles = default_encoder().encode_logits(masks_per_img, img_meta, thr)
+        else:
+            rles = default_encoder()(self.rescale_masks(masks_per_img, img_meta).float(), thr=thr)
         det_labels = labels_per_img.cpu().numpy()
         bboxes = np.zeros((len(rles), 5), dtype=np.float32)     # fake boxes: only the score column is filled
         bboxes[:, -1] = scores_per_img.cpu().numpy()

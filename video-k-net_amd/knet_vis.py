@@ -177,13 +177,40 @@ class KernelUpdateHeadVideo(_QueryMerge, KernelUpdateHead):
         tracks = outs2results(bboxes=bboxes, labels=labels_per_img, masks=seg_masks, ids=ids_per_img, num_classes=self.num_classes)
         return tracks['bbox_results'], tracks['mask_results']
 
+    def get_seg_masks_tracking_rle(self, masks_per_img, labels_per_img, scores_per_img, ids_per_img, test_cfg, img_meta, fused_rescale=False):
+        """`get_seg_masks_tracking` with the masks as COCO RLE dicts: `outs2results` packing (box rows [id, 0, 0, 0, 0, score], detections
+        with id < 0 dropped), the kept masks encoded on the device in one call, in the kept detections' order.  Only the kept rows are
+        rescaled.  fused_rescale=True: their masks come as bits straight from the logits (`MaskRLE.encode_logits` with `rows`)."""
+        import numpy as np
+        from .mask_rle import default_encoder
+        thr = float(self._meta(test_cfg, 'mask_thr'))
+        ids = ids_per_img.cpu().numpy() if torch.is_tensor(ids_per_img) else np.asarray(ids_per_img)
+        rows = torch.from_numpy(np.flatnonzero(ids > -1)).to(masks_per_img.device)
+        if rows.numel() == 0:
+            rles = []
+        elif fused_rescale:
+            rles = default_encoder().encode_logits(masks_per_img, img_meta, thr, rows=rows)
+        else:
+            rles = default_encoder()(self.rescale_masks(masks_per_img.index_select(0, rows), img_meta).float(), thr=thr)
+        bboxes = torch.zeros((masks_per_img.shape[0], 5), dtype=torch.float32)
+        bboxes[:, -1] = scores_per_img.cpu()
+        tracks = outs2results(bboxes=bboxes, labels=labels_per_img, ids=ids, num_classes=self.num_classes)
+        labels = (labels_per_img.cpu().numpy() if torch.is_tensor(labels_per_img) else np.asarray(labels_per_img))[ids > -1]
+        mask_results = [[] for _ in range(self.num_classes)]
+        for label, rle in zip(labels, rles):
+            mask_results[label].append(rle)
+        return tracks['bbox_results'], mask_results
+
     # the VIS head's instance results as COCO RLE dicts: the image head's method (rescale as above, threshold + encoding on the device)
     get_seg_masks_rle = KernelUpdateHead.get_seg_masks_rle
+    get_seg_masks_rle_fused = KernelUpdateHead.get_seg_masks_rle_fused
+    _seg_masks_rle = KernelUpdateHead._seg_masks_rle
     # ... and as device tensors for the mask-AP meter: the image head's method
     get_seg_masks_device = KernelUpdateHead.get_seg_masks_device
 
 
 KernelUpdateHead.get_seg_masks_tracking = KernelUpdateHeadVideo.get_seg_masks_tracking   # the per-frame head has it too (:484)
+KernelUpdateHead.get_seg_masks_tracking_rle = KernelUpdateHeadVideo.get_seg_masks_tracking_rle   # ... and its RLE twin
 
 
 def outs2results(bboxes=None, labels=None, masks=None, ids=None, num_classes=None, **kwargs):

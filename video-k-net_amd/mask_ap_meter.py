@@ -81,7 +81,36 @@ class MaskAPMeter:
         state = self._state(self.device if self.device is not None else dev)
         if dev != state.device:
             raise ValueError(f'MaskAPMeter.update: the meter lives on {state.device}, the masks on {dev}')
-        tables = ops.mask_overlap(dt_masks, gt_masks, thr=thr)
+        return self._match(image_id, ops.mask_overlap(dt_masks, gt_masks, thr=thr), dt_scores, dt_labels, gt_masks, gt_labels, gt_iscrowd, gt_area)
+
+    def update_logits(self, image_id, logits, img_meta, thr, dt_scores, dt_labels, gt_masks, gt_labels, gt_iscrowd=None, gt_area=None, rows=None, up=1):
+        """`update` with the detections straight from the head's mask logits: their masks, `rescale_masks(logits[rows]) > thr`, come as
+        bits (`ops.instance_mask_bits`, include/vkn_instmask.h) and only the ground truths are packed (vkn_bits_mask_overlap).  logits
+        float32 [N,Hm,Wm]: with up = 1 the scaled mask predictions, with up in (2, 4) the stride-8 logits; rows: the K detections' rows
+        (None: every row); dt_scores, dt_labels [K].  Geometries outside the kernel's envelope take the torch rescale and `update`."""
+        for t, name in ((logits, 'logits'), (gt_masks, 'gt_masks'), (dt_scores, 'dt_scores'), (dt_labels, 'dt_labels'), (gt_labels, 'gt_labels')):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise _lib.VknLibraryError(f'MaskAPMeter.update_logits: {name}: expected a CUDA/HIP tensor — the MI355X path has no CPU fallback')
+        if rows is not None:
+            rows = torch.as_tensor(rows, device=logits.device).reshape(-1)
+        K = int(logits.shape[0]) if rows is None else int(rows.numel())
+        if K == 0:
+            empty = torch.zeros((0, *(int(v) for v in img_meta['ori_shape'][:2])), dtype=torch.bool, device=logits.device)
+            return self.update(image_id, empty, dt_scores, dt_labels, gt_masks, gt_labels, gt_iscrowd, gt_area)
+        if not ops.instance_bits_fused(logits, img_meta, K, up):
+            sel = logits if rows is None else logits.index_select(0, rows.long())
+            return self.update(image_id, ops.rescale_masks_torch(sel.float(), img_meta, up), dt_scores, dt_labels, gt_masks, gt_labels, gt_iscrowd, gt_area,
+                               thr=float(thr))
+        dev = logits.device
+        state = self._state(self.device if self.device is not None else dev)
+        if dev != state.device:
+            raise ValueError(f'MaskAPMeter.update_logits: the meter lives on {state.device}, the logits on {dev}')
+        bits = ops.instance_mask_bits(logits, img_meta, thr, rows=rows, up=up)
+        tables = ops.mask_overlap_bits(bits, int(img_meta['ori_shape'][1]), gt_masks)
+        return self._match(image_id, tables, dt_scores, dt_labels, gt_masks, gt_labels, gt_iscrowd, gt_area)
+
+    def _match(self, image_id, tables, dt_scores, dt_labels, gt_masks, gt_labels, gt_iscrowd, gt_area):
+        dev, state = gt_masks.device, self._state_t
         G = int(gt_masks.shape[0])
         crowd = gt_iscrowd.to(device=dev, dtype=torch.uint8) if gt_iscrowd is not None else torch.zeros((G,), dtype=torch.uint8, device=dev)
         area = gt_area.to(device=dev, dtype=torch.float64) if gt_area is not None else None

@@ -52,13 +52,18 @@ class MaskRLE:
         if not need or (thr is not None and K * H * W * 4 >= 2 ** 31):
             raise _lib.VknError(-2, f'MaskRLE: {K} masks of {H} x {W} are outside the envelope of include/vkn_rle.h '
                                     f'(1 <= K <= {_C["VKN_RLE_MAX_K"]}, H * W < 2^31, K * H * W * element size < 2^31)')
-        b = self._buffers(masks.device)
+        return self._encode(K, H, W, masks.device, need, lambda head, b: ops.rle_encode(masks, head[:K * _REC], b['runs'], b['pool'], head[-1:], b['ws'][:need], thr=thr))
+
+    def _encode(self, K, H, W, device, need, call):
+        """The encode call (`call(head, buffers)`: head = the records, then the status word) with the one-retry rule: pools that were
+        reported full grow to the reported sizes, once."""
+        b = self._buffers(device)
         if b['ws'].numel() < need:
-            b['ws'] = torch.empty((need,), dtype=torch.uint8, device=masks.device)
-        head = torch.empty((K * _REC + 1,), dtype=torch.int32, device=masks.device)        # the records, then the status word
+            b['ws'] = torch.empty((need,), dtype=torch.uint8, device=device)
+        head = torch.empty((K * _REC + 1,), dtype=torch.int32, device=device)              # the records, then the status word
         for _ in range(2):
             head[-1:].zero_()
-            ops.rle_encode(masks, head[:K * _REC], b['runs'], b['pool'], head[-1:], b['ws'][:need], thr=thr)
+            call(head, b)
             self.device_calls += 1
             host = head.cpu().numpy()                                                      # one small device -> host copy
             rec, status = host[:-1].reshape(K, _REC), int(host[-1])
@@ -67,14 +72,36 @@ class MaskRLE:
             if not status & _C['VKN_RLE_STATUS_FULL']:
                 break
             if status & _C['VKN_RLE_STATUS_FULL_RUNS']:                                    # the records hold the true sizes: grow to them
-                b['runs'] = torch.empty((runs_used,), dtype=torch.int32, device=masks.device)
+                b['runs'] = torch.empty((runs_used,), dtype=torch.int32, device=device)
             if status & _C['VKN_RLE_STATUS_FULL_BYTES']:
-                b['pool'] = torch.empty((bytes_used,), dtype=torch.uint8, device=masks.device)
+                b['pool'] = torch.empty((bytes_used,), dtype=torch.uint8, device=device)
         else:
             raise _lib.VknError(-6, f'MaskRLE: pools of the reported sizes ({runs_used} runs, {bytes_used} bytes) were reported full again')
         raw = b['pool'][:bytes_used].cpu().numpy().tobytes()                               # the used prefix of the byte pool
         self._last = dict(K=K, H=H, W=W, rec=rec.copy(), raw=raw, buf=b, runs_used=runs_used)
         return self.counts()
+
+    def encode_logits(self, logits, img_meta, thr, rows=None, up=1):
+        """The RLEs of `rescale_masks(logits[rows]) > thr` without the K full-resolution maps: the masks come as bits straight from the
+        logits (`ops.instance_mask_bits`, include/vkn_instmask.h) and are encoded as they are (vkn_bits_rle_encode).  logits float32
+        [N,Hm,Wm]: with up = 1 the scaled mask predictions, with up in (2, 4) the head's stride-8 logits; rows: the entries to encode
+        (None: every row).  The same accessors and the same one-retry rule as a call.  CPU tensors and geometries outside the kernel's
+        envelope take the torch rescale and this encoder's call on its fp32 result."""
+        if not torch.is_tensor(logits) or logits.dim() != 3:
+            raise ValueError(f'MaskRLE.encode_logits: a tensor of logits [N,Hm,Wm], got {tuple(logits.shape) if torch.is_tensor(logits) else type(logits)}')
+        if rows is not None:
+            rows = torch.as_tensor(rows, device=logits.device).reshape(-1)
+        K = int(logits.shape[0]) if rows is None else int(rows.numel())
+        H, W = (int(v) for v in img_meta['ori_shape'][:2])
+        if K == 0:
+            return self(torch.zeros((0, H, W), dtype=torch.bool, device=logits.device))
+        if not ops.instance_bits_fused(logits, img_meta, K, up) or not ops.rle_bits_workspace_bytes(K, H, W):
+            sel = logits if rows is None else logits.index_select(0, rows.long())
+            return self(ops.rescale_masks_torch(sel.float(), img_meta, up), thr=float(thr))
+        self.device_calls = 0
+        bits = ops.instance_mask_bits(logits, img_meta, thr, rows=rows, up=up)
+        need = ops.rle_bits_workspace_bytes(K, H, W)
+        return self._encode(K, H, W, logits.device, need, lambda head, b: ops.rle_encode_bits(bits, W, head[:K * _REC], b['runs'], b['pool'], head[-1:], b['ws'][:need]))
 
     # ---- the last call
     def _need_last(self):

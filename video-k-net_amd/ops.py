@@ -1950,3 +1950,142 @@ def mask_ap_match(cfg, state, tables, scores, dt_labels, gt_labels, gt_crowd, gt
     with torch.cuda.device(state.device):
         check(_lib.lib().vkn_mask_ap_match(ctypes.byref(cfg), _ptr(state), state.numel(), opt(inter), opt(area_dt), opt(area_gt), opt(scores),
                                            opt(dt_labels), opt(gt_labels), opt(gt_crowd), opt(gt_area), K, G, int(image_seq), opt(match_gt), _stream()))
+
+
+# ---- instance masks as bits straight from the head's mask logits (include/vkn_instmask.h): the fused rescale, and the two consumers of bits
+def rescale_masks_torch(logits, img_meta, up=1):
+    """The reference's chain in torch, on the logits' device: interp_up (up > 1 only) -> sigmoid -> bilinear to batch_input_shape -> crop
+    to img_shape -> bilinear to ori_shape (knet/det/kernel_update_head.py:443-458).  -> float [K,Ho,Wo]."""
+    import torch.nn.functional as F
+    x = logits.unsqueeze(0)
+    if up > 1:
+        x = F.interpolate(x, scale_factor=up, mode='bilinear', align_corners=False)
+    h, w = img_meta['img_shape'][:2]
+    x = F.interpolate(x.sigmoid(), size=tuple(img_meta['batch_input_shape']), mode='bilinear', align_corners=False)[:, :, :h, :w]
+    return F.interpolate(x, size=tuple(img_meta['ori_shape'][:2]), mode='bilinear', align_corners=False).squeeze(0)
+
+
+def pack_mask_bits_torch(masks):
+    """bool [K,H,W] -> int64 [K, ceil(W / 64), H] in the layout of csrc/vkn_maskbits.h, in torch on the masks' device (the torch path of
+    `instance_mask_bits`: CPU tensors and geometries outside the envelope)."""
+    K, H, W = (int(s) for s in masks.shape)
+    NS = (W + 63) // 64
+    pad = torch.zeros((K, H, NS * 64), dtype=torch.int64, device=masks.device)
+    pad[:, :, :W] = masks.to(torch.int64)
+    words = (pad.view(K, H, NS, 64) << torch.arange(64, dtype=torch.int64, device=masks.device)).sum(-1)      # disjoint bits: the sum is the OR (bit 63 wraps to the sign)
+    return words.permute(0, 2, 1).contiguous()
+
+
+def instance_mask_cfg(Hm, Wm, img_meta, up=1):
+    """The `VknInstMaskCfg` of one image: logits [*, Hm, Wm], mmdet's img_meta (img_shape, batch_input_shape, ori_shape)."""
+    cfg = _lib.VknInstMaskCfg()
+    cfg.up, cfg.Hm, cfg.Wm = int(up), int(Hm), int(Wm)
+    cfg.Hb, cfg.Wb = (int(v) for v in img_meta['batch_input_shape'])
+    cfg.h, cfg.w = (int(v) for v in img_meta['img_shape'][:2])
+    cfg.Ho, cfg.Wo = (int(v) for v in img_meta['ori_shape'][:2])
+    return cfg
+
+
+def instance_bits_workspace_bytes(cfg, K):
+    """vkn_instance_bits_workspace_bytes: bytes of one call's workspace, 0 outside the envelope of include/vkn_instmask.h."""
+    return int(_lib.lib().vkn_instance_bits_workspace_bytes(ctypes.byref(cfg), int(K)))
+
+
+def instance_bits_fused(logits, img_meta, K, up=1):
+    """Does `instance_mask_bits` run the kernel for these logits (a CUDA float32 [N,Hm,Wm] tensor, a geometry inside the envelope), or
+    the torch path?"""
+    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3 and up in (1, 2, 4)):
+        return False
+    if any(int(v) >= 1 << 24 for v in (*logits.shape, *img_meta['batch_input_shape'], *img_meta['img_shape'][:2], *img_meta['ori_shape'][:2])):
+        return False
+    return instance_bits_workspace_bytes(instance_mask_cfg(logits.shape[1], logits.shape[2], img_meta, up), K) > 0
+
+
+def instance_mask_bits(logits, img_meta, thr, rows=None, up=1, status=None):
+    """Instance masks as bits (vkn_instance_bits_f32: one fill, one launch, no synchronisation): for entry k,
+    interp(interp(sigmoid(interp_up(logits[rows[k]])), batch_input_shape)[:h, :w], ori_shape) > thr.  logits float32 [N,Hm,Wm]: with
+    up = 1 the head's scaled mask predictions, with up in (2, 4) its stride-8 logits; rows: int tensor / list [K] (any order, duplicates
+    allowed) or None = every row; thr: one fp32 comparison, torch's `>`.  -> int64 [K, ceil(Wo / 64), Ho]: bit c of word [k, s, y] is
+    pixel (y, 64 s + c), the bits behind Wo are zero — what `rle_encode_bits` and `mask_overlap_bits` read.  `status`: an int32 [4] CUDA
+    tensor that takes the call's status word (VKN_INSTMASK_STATUS_*) instead of the stream's scratch buffer.
+    CPU tensors and geometries outside the envelope take the torch path: `rescale_masks_torch(...) > thr`, packed in torch."""
+    if not torch.is_tensor(logits) or logits.dim() != 3:
+        raise ValueError(f'instance_mask_bits: logits [N,Hm,Wm], got {tuple(logits.shape) if torch.is_tensor(logits) else type(logits)}')
+    N = int(logits.shape[0])
+    if rows is not None:
+        rows = torch.as_tensor(rows, device=logits.device).reshape(-1)
+    K = N if rows is None else int(rows.numel())
+    Ho, Wo = (int(v) for v in img_meta['ori_shape'][:2])
+    if K == 0:
+        return torch.zeros((0, (Wo + 63) // 64, Ho), dtype=torch.int64, device=logits.device)
+    if not instance_bits_fused(logits, img_meta, K, up):
+        sel = logits if rows is None else logits.index_select(0, rows.long())
+        return pack_mask_bits_torch(rescale_masks_torch(sel.float(), img_meta, up) > thr)
+    src = _req(logits, 'logits')
+    cfg = instance_mask_cfg(src.shape[1], src.shape[2], img_meta, up)
+    r = rows.to(torch.int32).contiguous() if rows is not None else None
+    bits = torch.empty((K, (Wo + 63) // 64, Ho), dtype=torch.int64, device=src.device)
+    need = _lib.INSTMASK['VKN_INSTMASK_WS_BYTES']
+    ws = _req_plain(status, 'status', torch.int32).view(torch.uint8)[:need] if status is not None else _workspace(need, src.device, scratch=True)[:need]
+    with torch.cuda.device(src.device):
+        check(_lib.lib().vkn_instance_bits_f32(ctypes.byref(cfg), _ptr(src), N, _ptr(r), K, float(thr), _ptr(bits), _ptr(ws), need, _stream()))
+    return bits
+
+
+def rle_bits_workspace_bytes(K, H, W):
+    """vkn_bits_rle_workspace_bytes: bytes of one `rle_encode_bits` call's workspace, 0 outside the envelope of include/vkn_rle.h."""
+    return int(_lib.lib().vkn_bits_rle_workspace_bytes(int(K), int(H), int(W)))
+
+
+def rle_encode_bits(bits, W, records, runs, pool, status, ws):
+    """`rle_encode` on masks that are bits already (vkn_bits_rle_encode, seven launches, no synchronisation).  bits int64
+    [K, ceil(W / 64), H] as `instance_mask_bits` returns them; the other tensors as in `rle_encode`, ws uint8
+    [rle_bits_workspace_bytes(K, H, W)]."""
+    b = _req_plain(bits, 'bits', torch.int64)
+    if b.dim() != 3 or b.shape[1] != (int(W) + 63) // 64:
+        raise ValueError(f'rle_encode_bits: bits [K, ceil(W / 64), H] for W = {W}, got {tuple(b.shape)}')
+    K, _, H = (int(s) for s in b.shape)
+    records, runs, status = (_req_plain(t, n, torch.int32) for t, n in ((records, 'records'), (runs, 'runs'), (status, 'status')))
+    pool, ws = _req_plain(pool, 'pool', torch.uint8), _req_plain(ws, 'ws', torch.uint8)
+    if records.numel() != K * _lib.RLE['VKN_RLE_RECORD_INTS'] or status.numel() < 1 or any(t.device != b.device for t in (records, runs, pool, status, ws)):
+        raise ValueError('rle_encode_bits: records int32 [K, VKN_RLE_RECORD_INTS], status int32 [1], everything on the bits\' device')
+    with torch.cuda.device(b.device):
+        check(_lib.lib().vkn_bits_rle_encode(_ptr(b), K, H, int(W), _ptr(records), _ptr(runs), runs.numel(), _ptr(pool), pool.numel(), _ptr(status),
+                                             _ptr(ws), ws.numel(), _stream()))
+
+
+def mask_overlap_bits_workspace_bytes(K, G, H, W):
+    """vkn_bits_mask_overlap_workspace_bytes: bytes of one `mask_overlap_bits` call's workspace (the ground truths as bits); 0 outside the
+    envelope of include/vkn_maskap.h and for G = 0."""
+    return int(_lib.lib().vkn_bits_mask_overlap_workspace_bytes(int(K), int(G), int(H), int(W)))
+
+
+def mask_overlap_bits(bits, W, gt, out=None):
+    """`mask_overlap` with the detections as bits (vkn_bits_mask_overlap: one pack and one overlap launch).  bits int64
+    [K, ceil(W / 64), H] as `instance_mask_bits` returns them; gt bool / uint8 [G,H,W].  -> (inter int64 [K,G], area_dt int64 [K],
+    area_gt int64 [G]); with `out` the call ADDS into that triple."""
+    d = _req_plain(bits, 'bits', torch.int64)
+    g = _req_bytes(gt, 'gt')
+    if d.dim() != 3 or g.dim() != 3 or d.shape[1] != (int(W) + 63) // 64 or int(g.shape[2]) != int(W) or g.shape[1] != d.shape[2] or d.device != g.device:
+        raise ValueError(f'mask_overlap_bits: bits [K, ceil(W / 64), H] and gt [G,H,W] of one size on one device, got {tuple(d.shape)} and {tuple(g.shape)}')
+    if g.data_ptr() % 16:
+        g = g.clone()
+    K, _, H = (int(s) for s in d.shape)
+    G, W = int(g.shape[0]), int(W)
+    need = mask_overlap_bits_workspace_bytes(K, G, H, W)
+    if (G and not need) or (K + G and not mask_overlap_workspace_bytes(K, G, H, W)):
+        raise _lib.VknError(-2, f'mask_overlap_bits: {K} x {G} masks of {H} x {W} are outside the envelope of include/vkn_maskap.h')
+    if out is None:
+        flat = torch.zeros((K * G + K + G + 6,), dtype=torch.int64, device=d.device)        # one fill; each table on a 16-byte boundary
+        a, b = (K * G + 1) // 2 * 2, (K * G + 1) // 2 * 2 + (K + 1) // 2 * 2
+        out = flat[:K * G].view(K, G), flat[a:a + K], flat[b:b + G]
+    inter, area_dt, area_gt = (_req_plain(t, n, torch.int64) for t, n in zip(out, ('inter', 'area_dt', 'area_gt')))
+    if tuple(inter.shape) != (K, G) or tuple(area_dt.shape) != (K,) or tuple(area_gt.shape) != (G,) or any(t.device != d.device for t in (inter, area_dt, area_gt)):
+        raise ValueError(f'mask_overlap_bits: out = (int64 [{K},{G}], int64 [{K}], int64 [{G}]) on the bits\' device')
+    if K + G == 0:
+        return inter, area_dt, area_gt
+    ws = _workspace(need, d.device, scratch=True)[:need] if need else None
+    opt = lambda t: _ptr(t if t is not None and t.numel() else None)          # noqa: E731  (an empty side travels as NULL)
+    with torch.cuda.device(d.device):
+        check(_lib.lib().vkn_bits_mask_overlap(opt(d), opt(g), K, G, H, W, opt(inter), opt(area_dt), opt(area_gt), opt(ws), need, _stream()))
+    return inter, area_dt, area_gt
