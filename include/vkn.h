@@ -270,7 +270,7 @@ int vkn_prepare_stage_f32(const VknDims* d, const VknStageWeights* w, void* prep
 
 /* ---- building block (unit tests, micro-benchmarks): out[M][Nout] = act(A[M][K] . W[Nout][K]^T + bias), act 0 none / 1 relu.
  *      w_split = NULL: exact-fp32 MFMA; else the bf16x3 planes of W produced by vkn_split_weight_f32
- *      (6 * roundup(Nout, 256) * K bytes: LDS tile images, K % 32 == 0).  ksplit > 1 splits K over workgroups (needs ws >= ksplit*M*Nout*4 bytes, Nout <= 256). */
+ *      (6 * roundup(Nout, 256) * K bytes, 16-byte aligned, else VKN_E_ALIGN: LDS tile images, K % 32 == 0).  ksplit > 1 splits K over workgroups (needs ws >= ksplit*M*Nout*4 bytes, Nout <= 256). */
 int vkn_split_weight_f32(const float* W, void* w_split, int Nout, int K, void* stream);
 int vkn_linear_f32(const float* A, const float* W, const void* w_split, const float* bias, float* out, int M, int K, int Nout,
                    int act, int ksplit, void* ws, size_t ws_bytes, void* stream);
@@ -282,7 +282,7 @@ int vkn_linear_f32(const float* A, const float* W, const void* w_split, const fl
  *
  *      vkn_split_weight_t_f32: the bf16x3 tile images of the TRANSPOSE of a stored matrix.  W is [K][Nout] row-major (a torch Linear
  *      weight [out = K][in = Nout]); the images describe Wt [Nout][K], so that `vkn_linear_f32(dY, ., images, ...)` with M rows,
- *      K = out features, Nout = in features computes dA = dY . W.  K % 32 == 0; 6 * roundup(Nout, 256) * K bytes.
+ *      K = out features, Nout = in features computes dA = dY . W.  K % 32 == 0; 6 * roundup(Nout, 256) * K bytes, 16-byte aligned (else VKN_E_ALIGN).
  *      vkn_linear_dw_f32: dW[n][k] (+)= sum_m dY[m][n] A[m][k]  ([Nout][K], the weight gradient of Y = A W^T),
  *      db[n] (+)= sum_m dY[m][n] (or NULL); ldy / lda = row strides of dY / A in floats; accumulate != 0 adds to dW / db.  Exact-fp32
  *      MFMA (v_mfma_f32_32x32x2_f32), deterministic. */

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(GM_THREADS) void k_gemm_r3(VknGemmProb p0, VknGemmP
         _Pragma("unroll") for (int e = 0; e < 2; ++e) {                                           \
             const float v_ = (mul ? S[0][e] * S[1][e] : S[0][e]) + (two ? S[2][e] * S[3][e] : 0.f); \
             __bf16 hh_, mm_, ll_;                                                                 \
-            vkn_split_bf16x3(v_, hh_, mm_, ll_);                                                  \
+            wimg::split3(v_, hh_, mm_, ll_);                                                  \
             h_[e] = hh_;                                                                          \
             m_[e] = mm_;                                                                          \
             l_[e] = ll_;                                                                          \
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(1024) void k_gemm_x16(VknGemmProb p0, VknGemmProb p
         _Pragma("unroll") for (int e = 0; e < 2; ++e) {                                           \
             const float v_ = (mul ? S[0][e] * S[1][e] : S[0][e]) + (two ? S[2][e] * S[3][e] : 0.f); \
             __bf16 hh_, mm_, ll_;                                                                 \
-            vkn_split_bf16x3(v_, hh_, mm_, ll_);                                                  \
+            wimg::split3(v_, hh_, mm_, ll_);                                                  \
             h_[e] = hh_;                                                                          \
             m_[e] = mm_;                                                                          \
             l_[e] = ll_;                                                                          \

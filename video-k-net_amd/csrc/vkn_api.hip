@@ -113,12 +113,6 @@ inline bool has_composites(const VknDims* d, const VknStageWeights* w) {
     return w->ft_w && w->ft_wT && w->ft_b && w->dyn_w && w->dyn_b && w->fc_mask_w && w->fc_mask_b && d->n_mask_fcs > 0;
 }
 
-struct PrepItem {
-    const float* src;
-    int nout, k;
-    const void** dst;
-};
-
 // (nout, k) of fp16 image i of the persistent chain (VKN_H2_* order); nout == 0: the image does not exist
 struct H2Shape { int nout, k; };
 inline H2Shape h2_shape(const VknDims* d, const VknStageWeights* w, int i) {
@@ -138,14 +132,17 @@ inline bool chain_width_ok(const VknDims* d) { return d->C == 256 && d->ff % 256
 inline bool chain_shape_ok(const VknDims* d) { return chain_width_ok(d) && d->n_cls_fcs == 1 && d->n_mask_fcs == 1; }
 
 // assigns slots inside `base` (may be null: size query) in a fixed order; returns total bytes.  `it` / `n_out` (vkn_prepare_stage_f32):
-// the (weight, shape, slot) list of the plain pre-split copies, in carve order
-size_t carve_prepared(const VknDims* d, const VknStageWeights* w, char* base, PrepW* p, PrepItem* it = nullptr, int* n_out = nullptr) {
+// the plain pre-split copies as items of the image writer (vkn_wimage.hip), in carve order
+// (`it` holds PREP_ITEMS: one per `add` call below, 18 + one per possible cls_fc / mask_fc layer; one table of the writer)
+constexpr int PREP_ITEMS = 18 + 2 * VKN_MAX_FCS;
+static_assert(PREP_ITEMS <= VKN_SPLIT_MAX_ITEMS, "the plain pre-split copies of a stage go to the image writer as ONE table");
+size_t carve_prepared(const VknDims* d, const VknStageWeights* w, char* base, PrepW* p, VknSplitItem* it = nullptr, int* n_out = nullptr) {
     const int C = d->C, FF = d->ff;
     Carver c{base, 0};
     int n = 0;
     auto add = [&](const float* src, int nout, int k, const void** dst) {
         *dst = src ? c.take<char>(vkn_split_w3_bytes(nout, k)) : nullptr;
-        if (src && it) it[n] = PrepItem{src, nout, k, dst};
+        if (src && it && n < PREP_ITEMS) it[n] = VknSplitItem{src, const_cast<void*>(*dst), k, 1, nout, k, k, 0};
         if (src) ++n;
     };
     add(w->ft_w, C, C, &p->ft); add(w->ft_wT, C, C, &p->ftT);
@@ -1273,12 +1270,14 @@ int vkn_prepare_stage_f32(const VknDims* d, const VknStageWeights* w, void* prep
     if (!w || !prepared) return VKN_E_ARG;
     if (!aligned16(prepared)) return VKN_E_ALIGN;
     PrepW pw;
-    PrepItem items[40];
+    VknSplitItem items[PREP_ITEMS];
     int n = 0;
     if (carve_prepared(d, w, static_cast<char*>(prepared), &pw, items, &n) > bytes) return VKN_E_WORKSPACE;
+    if (n > PREP_ITEMS) return VKN_E_ARG;   // (an `add` call that PREP_ITEMS does not count)
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int i = 0; i < n; ++i)
-        VKN_TRY(vkn_launch_split_w3(items[i].src, const_cast<void*>(*items[i].dst), items[i].nout, items[i].k, st));
+    // one launch.  The batch entry's own item checks cannot fire here: check_dims has passed (C, ff, ncls > 0; C, ff multiples of 32), every
+    // item has a source, and the slots are 256-byte offsets of a 16-byte aligned base
+    if (n > 0) VKN_TRY(vkn_split_weights_batch_f32(items, n, stream));
     if (pw.dynft) {
         // composite weights, exact-fp32 GEMMs (out[m][n] = sum_k A[m][k] W[n][k])
         const int C = d->C;

@@ -13,8 +13,8 @@
 //   * A workgroup (8 waves) OWNS 32 rows (kernels) for the whole launch.  Activations never leave the CU between GEMMs: they live in
 //     LDS as bf16x3 "images" [plane 3][row 32][k 256] (16-byte chunk j of row r stored at chunk j ^ r: conflict-free ds_read_b128) and,
 //     where a later epilogue needs them elementwise, in registers.
-//   * Weights are the pre-split bf16x3 tile images of vkn_prepare_stage_f32 ([plane][q][row 256][8] per 256-col x 32-k tile = already
-//     the MFMA fragment layout).  Wave w is the only consumer of column block w, so every wave streams ITS six fragments per K-tile
+//   * Weights are the pre-split bf16x3 tile images of vkn_prepare_stage_f32 (vkn_wimage.h: [plane][q][row 256][8] per 256-col x 32-k tile =
+//     already the MFMA fragment layout; the fragment address and the product group are that header's).  Wave w is the only consumer of column block w, so every wave streams ITS six fragments per K-tile
 //     straight from global memory (L2 / MALL resident: 12 MB per stage, read by all workgroups in near lock-step) into a 4-deep
 //     register ring with buffer loads — no LDS traffic for weights, no barrier inside a GEMM, and the stream never stops: the ring is
 //     refilled with the NEXT GEMM's first tiles while the current epilogue runs (the address sequence is static).
@@ -29,6 +29,7 @@
 //     for bit; everything is deterministic.
 #include "vkn_common.h"
 #include "vkn_launch.h"
+#include "vkn_wimage.h"
 
 // This file compiles TWICE: as itself (the three-term bf16 split: 6 bytes and 6 MFMAs per operand pair, 2^-24) and, with CH_H2 defined, from
 // vkn_chain_h2.hip (the TWO-term fp16 split hi + lo of the gather / decode kernels: 4 bytes, 3 MFMAs: what the persistent form runs unless VKN_FLAG_CHAIN_BF16X3).  Everything that
@@ -37,7 +38,6 @@
 #ifdef CH_H2
 typedef _Float16 ch_e;
 #define CH_NPL 2                        // planes per image / weight tile
-#define CH_WTILE 32768u                 // bytes of one weight tile image (256 cols x 32 k x 2 planes fp16)
 #define k_chain_a k_chain_a_h2
 #define k_chain_c k_chain_c_h2
 #define ChainAArgs ChainAArgsH2
@@ -47,8 +47,8 @@ typedef _Float16 ch_e;
 #else
 typedef __bf16 ch_e;
 #define CH_NPL 3
-#define CH_WTILE 49152u                 // bytes of one weight tile image (256 cols x 32 k x 3 planes bf16)
 #endif
+constexpr unsigned CH_WTILE = wimg::tile_bytes(CH_NPL);   // bytes of one weight tile image (vkn_wimage.h)
 typedef ch_e ch_ex8 __attribute__((ext_vector_type(8)));
 typedef ch_e ch_ex4 __attribute__((ext_vector_type(4)));
 typedef unsigned int cu32x4 __attribute__((ext_vector_type(4)));
@@ -66,21 +66,12 @@ typedef unsigned int cu32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-// v = p[0] + p[1] (+ p[2]): each term the rounding of what the earlier ones left
-__device__ __forceinline__ void ch_split(float v, ch_e (&p)[CH_NPL]) {
-    float r = v;
-#pragma unroll
-    for (int i = 0; i < CH_NPL; ++i) {
-        p[i] = (ch_e)r;
-        if (i + 1 < CH_NPL) r -= (float)p[i];
-    }
-}
 // four values -> CH_NPL packed 8-byte plane chunks
 __device__ __forceinline__ void ch_split4(const float (&v)[4], ch_ex4 (&o)[CH_NPL]) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         ch_e t[CH_NPL];
-        ch_split(v[e], t);
+        wimg::split(v[e], t);
 #pragma unroll
         for (int i = 0; i < CH_NPL; ++i) o[i][e] = t[i];
     }
@@ -109,7 +100,7 @@ __device__ __forceinline__ ChLane ch_lane(int tid) {
     L.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     L.g = lane >> 5;
     L.li = lane & 31;
-    L.woff = (unsigned)(L.g * 4096 + (L.wave * 32 + L.li) * 16);
+    L.woff = WIMG_FRAG_LANE_BYTES(L.g, L.wave * 32 + L.li);
     L.abase = (unsigned)(L.li * (CH_C * 2) + (((L.g ^ L.li) & 31) << 4));
     L.status = nullptr;
     return L;
@@ -147,7 +138,7 @@ __device__ __forceinline__ void ch_wload(ChRing<RING>& R, const int slot, const 
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int p = 0; p < NP; ++p)
-            R.r[slot][ks * CH_NPL + p] = __builtin_amdgcn_raw_buffer_load_b128(wrs, (int)L.woff, (int)(toff + (unsigned)((p * 4 + 2 * ks) * 4096)), AUX);
+            R.r[slot][ks * CH_NPL + p] = __builtin_amdgcn_raw_buffer_load_b128(wrs, (int)L.woff, (int)(toff + wimg::frag_step_bytes(p, ks)), AUX);
 }
 
 // activation fragments (CH_NPL planes) of K-tile kt, k-step ks from an image
@@ -162,22 +153,11 @@ __device__ __forceinline__ void ch_afrag(const ch_e* img, const ChLane& L, int k
 // W-fragments (slot) x activation fragments: the significant cross products, smallest first
 template <int RING>
 __device__ __forceinline__ void ch_mfma(f32x16& acc, const ChRing<RING>& R, const int slot, const int ks, const ch_ex8 (&a)[CH_NPL]) {
+    const cu32x4* w = R.r[slot] + ks * CH_NPL;
 #ifdef CH_H2
-    const ch_ex8 wh = __builtin_bit_cast(ch_ex8, R.r[slot][ks * 2 + 0]);
-    const ch_ex8 wl = __builtin_bit_cast(ch_ex8, R.r[slot][ks * 2 + 1]);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, a[0], acc, 0, 0, 0);   // lo x lo is below fp32 resolution
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, a[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, a[0], acc, 0, 0, 0);
+    wimg::mfma3<true>(acc, a[0], a[1], __builtin_bit_cast(ch_ex8, w[0]), __builtin_bit_cast(ch_ex8, w[1]));
 #else
-    const ch_ex8 wh = __builtin_bit_cast(ch_ex8, R.r[slot][ks * 3 + 0]);
-    const ch_ex8 wm = __builtin_bit_cast(ch_ex8, R.r[slot][ks * 3 + 1]);
-    const ch_ex8 wl = __builtin_bit_cast(ch_ex8, R.r[slot][ks * 3 + 2]);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, a[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, a[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, a[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, a[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, a[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, a[0], acc, 0, 0, 0);
+    wimg::mfma6<true>(acc, a[0], a[1], a[2], __builtin_bit_cast(ch_ex8, w[0]), __builtin_bit_cast(ch_ex8, w[1]), __builtin_bit_cast(ch_ex8, w[2]));
 #endif
 }
 #if defined(VKN_DEBUG) && !defined(CH_H2)
@@ -1088,7 +1068,7 @@ int vkn_launch_gemm_t3(const VknGemmProb* probs, int nprob, int M, int K, hipStr
         if (!p.Wsplit || (p.lda & 3) || (reinterpret_cast<uintptr_t>(p.A) & 15) || (p.A2 && (reinterpret_cast<uintptr_t>(p.A2) & 15)) ||
             (p.A3 && ((reinterpret_cast<uintptr_t>(p.A3) & 15) || !p.A4 || (reinterpret_cast<uintptr_t>(p.A4) & 15))))
             return VKN_E_SHAPE;
-        if ((size_t)((p.Nout + 255) / 256) * 8 * kc * CH_WTILE >= (1ull << 31)) return VKN_E_SHAPE;
+        if (wimg::image_bytes(CH_NPL, p.Nout, 256 * kc) >= (1ull << 31)) return VKN_E_SHAPE;
         nmax = p.Nout > nmax ? p.Nout : nmax;
     }
     const size_t lds = (size_t)kc * CH_IMG * sizeof(ch_e) + (size_t)2 * CH_SBUF * sizeof(float);
@@ -1173,31 +1153,6 @@ int vkn_chain_pack_consts(const VknChainConsts& c, float* out, hipStream_t strea
     return VKN_OK;
 }
 
-#else   // CH_H2: what only the fp16 form needs — its weight images
-// fp32 W [Nout][K] -> fp16 hi / lo tile images Wp[ceil(Nout/256)][K/32][2][4][256][8] of W * *scale (rows >= Nout zero), the layout of
-// k_split_w3 (vkn_update.hip) with two planes.  scale: DEVICE scalar, a power of two (vkn_pow2_scale_f32 of the matrix: its maximum at
-// 2^9 .. 2^10, so that the low half of every weight down to 2^-12 of the maximum keeps its eleven bits); grid = (K/32, ceil(Nout/256)).
-__global__ __launch_bounds__(256) void k_split_h2(const float* __restrict__ W, _Float16* __restrict__ Wp, int Nout, int K,
-                                                  const float* __restrict__ scale) {
-    const int kt = blockIdx.x, nt = blockIdx.y;
-    _Float16* dst = Wp + ((size_t)nt * gridDim.x + kt) * (CH_WTILE / 2);
-    const int row = threadIdx.x, n = nt * 256 + row;
-    const float sc = scale[0];
-    for (int k = 0; k < 32; ++k) {
-        ch_e t[2] = {(ch_e)0.f, (ch_e)0.f};
-        if (n < Nout) ch_split(W[(size_t)n * K + kt * 32 + k] * sc, t);
-        const int q = k >> 3, e = k & 7;
-        dst[((0 * 4 + q) * 256 + row) * 8 + e] = t[0];
-        dst[((1 * 4 + q) * 256 + row) * 8 + e] = t[1];
-    }
-}
-size_t vkn_split_h2_bytes(int Nout, int K) { return (size_t)((Nout + 255) / 256) * (size_t)(K / 32) * CH_WTILE; }
-int vkn_launch_split_h2(const float* W, void* images, int Nout, int K, const float* scale, hipStream_t stream) {
-    if (!W || !images || !scale || Nout <= 0 || K <= 0 || K % 32 != 0) return VKN_E_ARG;
-    hipLaunchKernelGGL(k_split_h2, dim3(K / 32, (Nout + 255) / 256), dim3(256), 0, stream, W, static_cast<_Float16*>(images), Nout, K, scale);
-    VKN_CHECK_LAUNCH();
-    return VKN_OK;
-}
 #endif  // CH_H2
 
 int vkn_launch_chain_a(const VknChainA& p, hipStream_t stream) {

@@ -5,7 +5,7 @@
 // Same source, compiled with CH_H2 (every difference hangs on that macro in vkn_chain.hip).  What the fp16 form adds is RANGE MANAGEMENT
 // — fp16 spans 2^-24 .. 65504, so a value keeps both halves' eleven bits only between 2^-3 and 2^16:
 //   * weight images: every matrix times ONE power of two that puts its maximum at 2^9 .. 2^10 (vkn_pow2_scale_f32 at prepare time;
-//     k_split_h2); the inverse travels in the constant block and multiplies the accumulators behind each GEMM — exact;
+//     the two-plane writer of vkn_wimage.hip); the inverse travels in the constant block and multiplies the accumulators behind each GEMM — exact;
 //   * activation images whose row magnitude the chain does not bound — the raw gather sums / x_feat, the incoming kernels, the
 //     attention output, the updator's gate product (input_in x parameters_in) — are scaled ROW BY ROW by the power of two of the
 //     row's maximum (a lane of the transposed accumulator tile owns one row: the inverse is one more factor of the same multiply);

@@ -12,8 +12,8 @@
 //
 // Design (DESIGN.md §5 "few-row chain"):
 //   * Workgroup = 32 MT rows x 32 NCB output columns, 8 waves; wave w owns K-tile(s) w of the 256 KPW-wide contraction chunk: it
-//     requests ITS six weight fragments per (column block, K-tile) — the pre-split bf16x3 tile images of vkn_prepare_stage_f32,
-//     already the MFMA operand layout — and ITS 32-wide slice of the activation rows straight from global memory into registers, all
+//     requests ITS six weight fragments per (column block, K-tile) — the pre-split bf16x3 tile images of vkn_prepare_stage_f32
+//     (vkn_wimage.h), already the MFMA operand layout — and ITS 32-wide slice of the activation rows straight from global memory into registers, all
 //     at once: ONE round trip, no LDS staging, no K loop.  117 rows x 256 columns = 32 workgroups instead of 4; the FFN 256.
 //   * Row-wise normalisation moves from the PRODUCER's epilogue (which would need whole rows in one workgroup) to the CONSUMER's
 //     prologue: a GEMM stores its raw output (+ bias, + residual) and the next GEMM applies LayerNorm / ReLU / sigmoid / the updator's
@@ -33,6 +33,7 @@
 // boundary is the cheaper seam.
 #include "vkn_common.h"
 #include "vkn_launch.h"
+#include "vkn_wimage.h"
 
 // Floating-point contraction is OFF in this file: the same phase runs in several tile shapes (NCB, MT) picked by row count, and hipcc
 // contracts `a * b + c` into an fma in one instantiation and not in another (seen: the count-scaled bias `bias * count + bias2` of the
@@ -45,20 +46,13 @@ typedef unsigned int ku32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 khalf2 __attribute__((ext_vector_type(2)));
 
 #define KS_THREADS 512
-#define KS_WTILE 49152u
+constexpr unsigned KS_WTILE = wimg::tile_bytes(3);   // bytes of one weight tile image (vkn_wimage.h)
 #define KS_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 // pin a loaded value HERE: hipcc otherwise sinks a load whose only use sits behind a (uniform) branch into that branch — behind the
 // wait for the activation rows, i.e. a second memory round trip for every optional vector of the prologue / epilogue
 #define KS_PIN(x) asm volatile("" : "+v"(x))
 
 namespace {
-
-__device__ __forceinline__ void ks_split3(float v, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)v;
-    const float r1 = v - (float)h;
-    m = (__bf16)r1;
-    l = (__bf16)(r1 - (float)m);
-}
 
 // this lane's 16 values of a 32-wide k-slice: p points at (row, slice base + 8 g); k-step 0 = p[0..7], k-step 1 = p[16..23]
 __device__ __forceinline__ void ks_load16(const float* __restrict__ p, float (&o)[16]) {
@@ -183,7 +177,7 @@ __global__ __launch_bounds__(KS_THREADS) void k_gemm_ks(const VknKsProb p0, cons
     {
         const int ntile = (P.Nout + 255) >> 8;
         const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(P.Wsplit), 0, (int)((unsigned)(ntile * P.KT) * KS_WTILE), 0x00020000);
-        const unsigned voff = (unsigned)(g * 4096 + ((cb0 & 7) * 32 + li) * 16);
+        const unsigned voff = WIMG_FRAG_LANE_BYTES(g, (cb0 & 7) * 32 + li);
         const unsigned tbase = (unsigned)((cb0 >> 3) * P.KT + (kz * 8 + wave) * KPW) * KS_WTILE;
 #pragma unroll
         for (int c = 0; c < NCB; ++c)
@@ -194,7 +188,7 @@ __global__ __launch_bounds__(KS_THREADS) void k_gemm_ks(const VknKsProb p0, cons
 #pragma unroll
                     for (int p = 0; p < 3; ++p)
                         wf[c][j][ks * 3 + p] = __builtin_amdgcn_raw_buffer_load_b128(wrs, (int)(voff + (unsigned)c * 512u),
-                                                                                     (int)(tbase + (unsigned)j * KS_WTILE + (unsigned)((p * 4 + 2 * ks) * 4096)), 0);
+                                                                                     (int)(tbase + (unsigned)j * KS_WTILE + wimg::frag_step_bytes(p, ks)), 0);
     }
 
     int rowc[MT];
@@ -382,7 +376,7 @@ __global__ __launch_bounds__(KS_THREADS) void k_gemm_ks(const VknKsProb p0, cons
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     __bf16 hh, mm, ll;
-                    ks_split3(av[mt][j][8 * ks + e], hh, mm, ll);
+                    wimg::split3(av[mt][j][8 * ks + e], hh, mm, ll);
                     ah[e] = hh;
                     am[e] = mm;
                     al[e] = ll;
@@ -392,13 +386,7 @@ __global__ __launch_bounds__(KS_THREADS) void k_gemm_ks(const VknKsProb p0, cons
                     const kbf16x8 wh = __builtin_bit_cast(kbf16x8, wf[c][j][ks * 3 + 0]);
                     const kbf16x8 wm = __builtin_bit_cast(kbf16x8, wf[c][j][ks * 3 + 1]);
                     const kbf16x8 wl = __builtin_bit_cast(kbf16x8, wf[c][j][ks * 3 + 2]);
-                    f32x16& A = acc[mt * NCB + c];
-                    A = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, ah, A, 0, 0, 0);
-                    A = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, al, A, 0, 0, 0);
-                    A = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, am, A, 0, 0, 0);
-                    A = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, ah, A, 0, 0, 0);
-                    A = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, am, A, 0, 0, 0);
-                    A = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, ah, A, 0, 0, 0);
+                    wimg::mfma6<true>(acc[mt * NCB + c], ah, am, al, wh, wm, wl);
                 }
             }
 
@@ -467,7 +455,7 @@ int vkn_launch_gemm_ks(const VknKsProb* probs, int nprob, int mode, int zchunks,
     for (int i = 0; i < nprob; ++i) {
         const VknKsProb& p = probs[i];
         if (!p.Wsplit || p.Nout <= 0 || p.KT < 8 * kpw * (zchunks > 0 ? zchunks : 1)) return VKN_E_ARG;
-        if ((size_t)((p.Nout + 255) / 256) * p.KT * KS_WTILE >= (1ull << 31)) return VKN_E_SHAPE;
+        if (wimg::image_bytes(3, p.Nout, 32 * p.KT) >= (1ull << 31)) return VKN_E_SHAPE;
         const int nop = mode == 0 ? 1 : (mode == 1 ? 2 : 4);
         for (int k = 0; k < nop; ++k)
             if (!p.pro.a[k] || (p.pro.lda[k] & 3) || (reinterpret_cast<uintptr_t>(p.pro.a[k]) & 15)) return VKN_E_SHAPE;

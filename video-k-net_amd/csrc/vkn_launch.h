@@ -34,7 +34,7 @@ struct VknGemmProb {
     const float* A4;
     int lda;
     const float* W;      // fp32 [Nout][K]
-    const void* Wsplit;  // or null: bf16x3 planes of W (k_split_w3)
+    const void* Wsplit;  // or null: the bf16x3 tile images of W (vkn_wimage.h)
     int Nout;
     VknEpi epi;
 };

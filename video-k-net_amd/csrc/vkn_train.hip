@@ -273,77 +273,6 @@ __global__ __launch_bounds__(TL_THREADS, 2) void k_gemm_tn_batch(const TnTab T, 
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------------ k_split_batch
-// The bf16x3 tile images of MANY weights in one launch (both orientations of every Linear weight of a stage: the weights change every
-// training step).  Image layout as k_split_w3 (vkn_update.hip): [ceil(Nout/256)][K/32][plane 3][q 4][row 256][8] bf16.  A workgroup writes
-// one 48-KB tile: thread = row, 32 k values -> twelve 16-byte stores, consecutive threads consecutive 16 bytes.
-struct SplitTab {
-    const float* W[VKN_SPLIT_MAX_ITEMS];
-    __bf16* dst[VKN_SPLIT_MAX_ITEMS];
-    long long ldn[VKN_SPLIT_MAX_ITEMS], ldk[VKN_SPLIT_MAX_ITEMS];
-    int nout[VKN_SPLIT_MAX_ITEMS], k[VKN_SPLIT_MAX_ITEMS], kvalid[VKN_SPLIT_MAX_ITEMS];
-    int tile0[VKN_SPLIT_MAX_ITEMS + 1];
-};
-
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split3(float v, unsigned short& h, unsigned short& m, unsigned short& l) {
-    const __bf16 bh = (__bf16)v;
-    const float r1 = v - (float)bh;
-    const __bf16 bm = (__bf16)r1;
-    const __bf16 bl = (__bf16)(r1 - (float)bm);
-    h = __builtin_bit_cast(unsigned short, bh);
-    m = __builtin_bit_cast(unsigned short, bm);
-    l = __builtin_bit_cast(unsigned short, bl);
-}
-
-__global__ __launch_bounds__(256) void k_split_batch(const SplitTab T, int nitems) {
-    const int b = blockIdx.x;
-    int it = 0;
-    while (it + 1 < nitems && b >= T.tile0[it + 1]) ++it;   // block-uniform
-    const int tl = b - T.tile0[it];
-    const int K = T.k[it], Nout = T.nout[it], kvalid = T.kvalid[it];
-    const int ktiles = K >> 5;
-    const int nt = tl / ktiles, kt = tl - nt * ktiles;
-    const float* __restrict__ W = T.W[it];
-    const long long ldn = T.ldn[it], ldk = T.ldk[it];
-    const int row = threadIdx.x, n = nt * 256 + row;
-    float v[32];
-    if (n < Nout) {
-        if (ldk == 1 && kt * 32 + 32 <= kvalid && (ldn & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0) {
-            const f32x4* src = reinterpret_cast<const f32x4*>(W + (size_t)n * ldn + kt * 32);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const f32x4 t = src[j];
-                v[4 * j] = t[0]; v[4 * j + 1] = t[1]; v[4 * j + 2] = t[2]; v[4 * j + 3] = t[3];
-            }
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < 32; ++kk) {
-                const int k = kt * 32 + kk;
-                v[kk] = k < kvalid ? W[(size_t)n * ldn + (size_t)k * ldk] : 0.f;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int kk = 0; kk < 32; ++kk) v[kk] = 0.f;
-    }
-    u16x8* dst = reinterpret_cast<u16x8*>(T.dst[it] + ((size_t)nt * ktiles + kt) * (3 * 4 * 256 * 8));
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        u16x8 h, m, l;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            unsigned short a, c, d;
-            split3(v[8 * q + e], a, c, d);
-            h[e] = a; m[e] = c; l[e] = d;
-        }
-        dst[(0 * 4 + q) * 256 + row] = h;
-        dst[(1 * 4 + q) * 256 + row] = m;
-        dst[(2 * 4 + q) * 256 + row] = l;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------ LayerNorm
 constexpr int LN_MAXV = 4;   // C <= 256: up to four elements per lane
 
@@ -1132,32 +1061,6 @@ int vkn_linear_dw_f32(const float* dY, int ldy, const float* A, int lda, float* 
     VKN_CHECK_LAUNCH();
     return VKN_OK;
 }
-
-int vkn_split_weights_batch_f32(const VknSplitItem* items, int nitems, void* stream) {
-    if (!items || nitems <= 0 || nitems > VKN_SPLIT_MAX_ITEMS) return VKN_E_ARG;
-    SplitTab T;
-    int tiles = 0;
-    for (int i = 0; i < nitems; ++i) {
-        const VknSplitItem& it = items[i];
-        if (!it.W || !it.images || it.Nout <= 0 || it.K <= 0 || it.kvalid < 0 || it.kvalid > it.K) return VKN_E_ARG;
-        if (it.K % 32 != 0 || (reinterpret_cast<uintptr_t>(it.images) & 15) != 0) return VKN_E_SHAPE;
-        T.W[i] = it.W;
-        T.dst[i] = static_cast<__bf16*>(it.images);
-        T.ldn[i] = it.ldn;
-        T.ldk[i] = it.ldk;
-        T.nout[i] = it.Nout;
-        T.k[i] = it.K;
-        T.kvalid[i] = it.kvalid;
-        T.tile0[i] = tiles;
-        tiles += ((it.Nout + 255) / 256) * (it.K / 32);
-    }
-    T.tile0[nitems] = tiles;
-    hipLaunchKernelGGL(k_split_batch, dim3(tiles), dim3(256), 0, static_cast<hipStream_t>(stream), T, nitems);
-    VKN_CHECK_LAUNCH();
-    return VKN_OK;
-}
-
-size_t vkn_sizeof_split_item(void) { return sizeof(VknSplitItem); }
 
 size_t vkn_sizeof_dw_item(void) { return sizeof(VknDwItem); }
 size_t vkn_sizeof_updator_norms(void) { return sizeof(VknUpdatorNorms); }

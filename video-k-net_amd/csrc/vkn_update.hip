@@ -21,6 +21,7 @@
 //   k_upsample  bilinear, align_corners=False, integer scale.
 #include "vkn_common.h"
 #include "vkn_launch.h"
+#include "vkn_wimage.h"
 
 
 #define GM_THREADS 512
@@ -265,8 +266,9 @@ __global__ __launch_bounds__(GM_THREADS, 2) void k_gemm(const float* __restrict_
 // The kernel-update chain is a sequence of short dependent kernels on M ~ 10^3 rows, so what matters is the serial latency of
 // one launch.  tools/gemm_trace.sh showed the per-K-tile phases {L1 fill of the 48 KB weight tile, LDS write, LDS read + MFMA,
 // two barriers} each cost 0.3-0.5 us and serialised (1.2 us per K-tile).  This version overlaps them:
-//   * weights are PRE-SPLIT (k_split_w3, once per weight update) into the exact LDS image of a (256-column, 32-k) tile —
-//     Wp[col tile][k tile][plane 3][q 4][row 256][8 bf16], 48 KB contiguous — and stream global -> LDS with
+//   * weights are PRE-SPLIT (once per weight update) into the tile images of vkn_wimage.h — layout, split, fragment address and product
+//     group are defined there, the writer is vkn_wimage.hip — i.e. the exact LDS image of a (256-column, 32-k) tile,
+//     Wp[col tile][k tile][plane 3][q 4][row 256][8 bf16], 48 KB contiguous, and stream global -> LDS with
 //     `global_load_lds_dwordx4` (no VGPR round trip, no ds_write); a fragment read (fixed plane/q, 32 consecutive rows) is
 //     32 consecutive 16-B slots: conflict-free;
 //   * A [M][lda] fp32 is split in registers while it is staged (4 KB per tile);
@@ -275,32 +277,12 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 #define GS_LDR 40                   // bf16 per LDS row of the A image: 32 + 8 pad (80 B: conflict-free ds_read_b128)
-#define GS_WTILE (3 * 4 * 256 * 8)  // bf16 elements of one weight tile image (48 KB)
+constexpr int GS_WTILE = wimg::tile_elems(3);  // bf16 elements of one weight tile image (48 KB)
 #define GS_ATILE (3 * GM_BM * GS_LDR)
-
-__device__ __forceinline__ void vkn_split_bf16x3(float v, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)v;
-    const float r1 = v - (float)h;
-    m = (__bf16)r1;
-    l = (__bf16)(r1 - (float)m);
-}
-
-// fp32 W [Nout][K] -> tile images Wp[ceil(Nout/256)][K/32][3][4][256][8] (rows >= Nout zero).  grid = (K/32, ceil(Nout/256)).
-// Element (n, k) of the weight is read at W[n * ldn + k * ldk]: (K, 1) for a torch Linear weight, (1, Nout) for the images of its
-// TRANSPOSE (the dA = dY . W GEMM of the backward pass: "weight" [K_fwd][Nout_fwd] read from the same storage).
-__global__ __launch_bounds__(256) void k_split_w3(const float* __restrict__ W, __bf16* __restrict__ Wp, int Nout, int K, size_t ldn,
-                                                  size_t ldk) {
-    const int kt = blockIdx.x, nt = blockIdx.y;
-    __bf16* dst = Wp + ((size_t)nt * gridDim.x + kt) * GS_WTILE;
-    const int row = threadIdx.x, n = nt * 256 + row;
-    for (int k = 0; k < 32; ++k) {
-        __bf16 h = (__bf16)0.f, m = (__bf16)0.f, l = (__bf16)0.f;
-        if (n < Nout) vkn_split_bf16x3(W[(size_t)n * ldn + (size_t)(kt * 32 + k) * ldk], h, m, l);
-        const int q = k >> 3, e = k & 7;
-        dst[((0 * 4 + q) * 256 + row) * 8 + e] = h;
-        dst[((1 * 4 + q) * 256 + row) * 8 + e] = m;
-        dst[((2 * 4 + q) * 256 + row) * 8 + e] = l;
-    }
+// acc += (activation fragments ah + am + al) x (the three planes of the weight fragment at bp, an LDS copy of a tile)
+__device__ __forceinline__ void gs_wmfma6(f32x16& acc, bf16x8 ah, bf16x8 am, bf16x8 al, const __bf16* bp) {
+    wimg::mfma6<false>(acc, ah, am, al, *reinterpret_cast<const bf16x8*>(bp), *reinterpret_cast<const bf16x8*>(bp + wimg::PLANE),
+                       *reinterpret_cast<const bf16x8*>(bp + 2 * wimg::PLANE));
 }
 
 // Up to two independent problems (same M, K) run as ONE launch, selected by blockIdx.z when ksplit == 1: pairing independent
@@ -374,7 +356,7 @@ __global__ __launch_bounds__(GM_THREADS) void k_gemm_s3(VknGemmProb p0, VknGemmP
         _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                           \
             const float v_ = (mul ? S[0][e] * S[1][e] : S[0][e]) + (two ? S[2][e] * S[3][e] : 0.f); \
             __bf16 hh_, mm_, ll_;                                                                 \
-            vkn_split_bf16x3(v_, hh_, mm_, ll_);                                                  \
+            wimg::split3(v_, hh_, mm_, ll_);                                                  \
             h_[e] = hh_;                                                                          \
             m_[e] = mm_;                                                                          \
             l_[e] = ll_;                                                                          \
@@ -392,19 +374,11 @@ __global__ __launch_bounds__(GM_THREADS) void k_gemm_s3(VknGemmProb p0, VknGemmP
             const __bf16* Wb = Wl + (size_t)((I) % 3) * GS_WTILE;                                                     \
             _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                        \
                 const __bf16* ap = Ab + li * GS_LDR + (ks << 4) + (g << 3);                                           \
-                const __bf16* bp = Wb + (((ks << 1) + g) * 256 + wave * 32 + li) * 8; /* plane 0, q = 2*ks + g */     \
+                const __bf16* bp = Wb + WIMG_FRAG_ELEM(ks, g, wave * 32, li);                                         \
                 const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ap);                                               \
                 const bf16x8 am = *reinterpret_cast<const bf16x8*>(ap + GM_BM * GS_LDR);                              \
                 const bf16x8 al = *reinterpret_cast<const bf16x8*>(ap + 2 * GM_BM * GS_LDR);                          \
-                const bf16x8 bh = *reinterpret_cast<const bf16x8*>(bp);                                               \
-                const bf16x8 bm = *reinterpret_cast<const bf16x8*>(bp + 4 * 256 * 8);                                 \
-                const bf16x8 bl = *reinterpret_cast<const bf16x8*>(bp + 8 * 256 * 8);                                 \
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0); /* smallest terms first */       \
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);                                  \
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);                                  \
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc, 0, 0, 0);                                  \
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc, 0, 0, 0);                                  \
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);                                  \
+                gs_wmfma6(acc, ah, am, al, bp);                                                                       \
             }                                                                                                         \
         }                                                                                                             \
     } while (0)
@@ -561,7 +535,7 @@ __global__ __launch_bounds__(GM_THREADS, 2) void k_ffn_fused(const float* __rest
             bf16x4 h_, m_, l_;                                                                        \
             _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                           \
                 __bf16 hh_, mm_, ll_;                                                                 \
-                vkn_split_bf16x3(ra[e], hh_, mm_, ll_);                                               \
+                wimg::split3(ra[e], hh_, mm_, ll_);                                               \
                 h_[e] = hh_;                                                                          \
                 m_[e] = mm_;                                                                          \
                 l_[e] = ll_;                                                                          \
@@ -571,18 +545,6 @@ __global__ __launch_bounds__(GM_THREADS, 2) void k_ffn_fused(const float* __rest
             *reinterpret_cast<bf16x4*>(d_ + GM_BM * GS_LDR) = m_;                                     \
             *reinterpret_cast<bf16x4*>(d_ + 2 * GM_BM * GS_LDR) = l_;                                 \
         }                                                                                             \
-    } while (0)
-#define FF_MFMA6(ACC, AH, AM, AL, BP)                                                                 \
-    do {                                                                                              \
-        const bf16x8 bh_ = *reinterpret_cast<const bf16x8*>(BP);                                      \
-        const bf16x8 bm_ = *reinterpret_cast<const bf16x8*>((BP) + 4 * 256 * 8);                      \
-        const bf16x8 bl_ = *reinterpret_cast<const bf16x8*>((BP) + 8 * 256 * 8);                      \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AH, bl_, ACC, 0, 0, 0);                         \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AL, bh_, ACC, 0, 0, 0);                         \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AM, bm_, ACC, 0, 0, 0);                         \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AH, bm_, ACC, 0, 0, 0);                         \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AM, bh_, ACC, 0, 0, 0);                         \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AH, bh_, ACC, 0, 0, 0);                         \
     } while (0)
 
     f32x16 acc2;
@@ -623,8 +585,8 @@ __global__ __launch_bounds__(GM_THREADS, 2) void k_ffn_fused(const float* __rest
                     const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ap);
                     const bf16x8 am = *reinterpret_cast<const bf16x8*>(ap + GM_BM * GS_LDR);
                     const bf16x8 al = *reinterpret_cast<const bf16x8*>(ap + 2 * GM_BM * GS_LDR);
-                    const __bf16* bp = Wb + (((ks << 1) + g) * 256 + wave * 32 + li) * 8;
-                    FF_MFMA6(acc1, ah, am, al, bp);
+                    const __bf16* bp = Wb + WIMG_FRAG_ELEM(ks, g, wave * 32, li);
+                    gs_wmfma6(acc1, ah, am, al, bp);
                 }
             }
             if (more) FF_ASTASH(cur ^ 1);
@@ -638,7 +600,7 @@ __global__ __launch_bounds__(GM_THREADS, 2) void k_ffn_fused(const float* __rest
             for (int r = 0; r < 16; ++r) {
                 const float v = fmaxf(acc1[r] + bias, 0.f);
                 __bf16 hh, mm, ll;
-                vkn_split_bf16x3(v, hh, mm, ll);
+                wimg::split3(v, hh, mm, ll);
                 const int row = vkn_cd_row(r, lane);
                 __bf16* d = Hl + row * FF_HLD + ((((col >> 3) ^ row) & 31) << 3) + (col & 7);
                 d[0] = hh;
@@ -664,8 +626,8 @@ __global__ __launch_bounds__(GM_THREADS, 2) void k_ffn_fused(const float* __rest
                     const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ap);
                     const bf16x8 am = *reinterpret_cast<const bf16x8*>(ap + GM_BM * FF_HLD);
                     const bf16x8 al = *reinterpret_cast<const bf16x8*>(ap + 2 * GM_BM * FF_HLD);
-                    const __bf16* bp = Wb + (((ks << 1) + g) * 256 + wave * 32 + li) * 8;
-                    FF_MFMA6(acc2, ah, am, al, bp);
+                    const __bf16* bp = Wb + WIMG_FRAG_ELEM(ks, g, wave * 32, li);
+                    gs_wmfma6(acc2, ah, am, al, bp);
                 }
             }
             if (!VKN_ABL_IS(ABL, 1)) FF_VMCNT0();
@@ -674,7 +636,6 @@ __global__ __launch_bounds__(GM_THREADS, 2) void k_ffn_fused(const float* __rest
     }
 #undef FF_DMA
 #undef FF_ASTASH
-#undef FF_MFMA6
 #undef FF_VMCNT0
 
     float* pz = partial + (size_t)hs * M * C;
@@ -969,7 +930,7 @@ __global__ __launch_bounds__(256) void k_attn_mfma(const float* __restrict__ Q, 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             __bf16 hh, mm, ll;
-            vkn_split_bf16x3(kv[e], hh, mm, ll);
+            wimg::split3(kv[e], hh, mm, ll);
             kh[e] = hh;
             km[e] = mm;
             kl[e] = ll;
@@ -993,7 +954,7 @@ __global__ __launch_bounds__(256) void k_attn_mfma(const float* __restrict__ Q, 
         for (int e = 0; e < 4; ++e) {
             const float v = (j + e < Nk) ? vreg[it][e] : 0.f;
             __bf16 hh, mm, ll;
-            vkn_split_bf16x3(v, hh, mm, ll);
+            wimg::split3(v, hh, mm, ll);
             vh[e] = hh;
             vm[e] = mm;
             vl[e] = ll;
@@ -1017,7 +978,7 @@ __global__ __launch_bounds__(256) void k_attn_mfma(const float* __restrict__ Q, 
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             __bf16 hh, mm, ll;
-            vkn_split_bf16x3((e < 4 ? qreg[ks][0][e] : qreg[ks][1][e - 4]) * scale, hh, mm, ll);
+            wimg::split3((e < 4 ? qreg[ks][0][e] : qreg[ks][1][e - 4]) * scale, hh, mm, ll);
             qh[ks][e] = hh;
             qm[ks][e] = mm;
             ql[ks][e] = ll;
@@ -1075,7 +1036,7 @@ __global__ __launch_bounds__(256) void k_attn_mfma(const float* __restrict__ Q, 
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 __bf16 hh, mm, ll;
-                vkn_split_bf16x3(acc[kb][8 * hf + e] * inv, hh, mm, ll);
+                wimg::split3(acc[kb][8 * hf + e] * inv, hh, mm, ll);
                 ph[e] = hh;
                 pm[e] = mm;
                 pl[e] = ll;
@@ -1336,9 +1297,6 @@ int vkn_launch_gemm(const float* A, const float* A2, int lda, const float* W, co
     return vkn_launch_gemm_group(&p, 1, M, K, ksplit, partial, stream);
 }
 
-// bytes of the pre-split tile images of a [Nout][K] weight
-size_t vkn_split_w3_bytes(int Nout, int K) { return (size_t)((Nout + 255) / 256) * (K / 32) * GS_WTILE * sizeof(__bf16); }
-
 __global__ void k_transpose(const float* __restrict__ src, float* __restrict__ dst, int R, int Cc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= R * Cc) return;
@@ -1349,24 +1307,6 @@ __global__ void k_transpose(const float* __restrict__ src, float* __restrict__ d
 int vkn_launch_transpose(const float* src, float* dst, int R, int Cc, hipStream_t st) {
     const int n = R * Cc;
     hipLaunchKernelGGL(k_transpose, dim3((n + 255) / 256), dim3(256), 0, st, src, dst, R, Cc);
-    VKN_CHECK_LAUNCH();
-    return VKN_OK;
-}
-
-// fp32 W [Nout][K] -> tile images (K % 32 == 0)
-int vkn_launch_split_w3(const float* W, void* Wp, int Nout, int K, hipStream_t stream) {
-    if (Nout <= 0 || K <= 0 || K % 32 != 0) return VKN_E_SHAPE;
-    hipLaunchKernelGGL(k_split_w3, dim3(K / 32, (Nout + 255) / 256), dim3(256), 0, stream, W, static_cast<__bf16*>(Wp), Nout, K,
-                       (size_t)K, (size_t)1);
-    VKN_CHECK_LAUNCH();
-    return VKN_OK;
-}
-
-// tile images of the TRANSPOSE of a stored matrix: Wt [Nout][K] with Wt[n][k] = W[k * Nout + n] (W is [K][Nout] row-major)
-int vkn_launch_split_w3_t(const float* W, void* Wp, int Nout, int K, hipStream_t stream) {
-    if (Nout <= 0 || K <= 0 || K % 32 != 0) return VKN_E_SHAPE;
-    hipLaunchKernelGGL(k_split_w3, dim3(K / 32, (Nout + 255) / 256), dim3(256), 0, stream, W, static_cast<__bf16*>(Wp), Nout, K,
-                       (size_t)1, (size_t)Nout);
     VKN_CHECK_LAUNCH();
     return VKN_OK;
 }
