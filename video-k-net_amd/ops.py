@@ -2089,3 +2089,36 @@ def mask_overlap_bits(bits, W, gt, out=None):
     with torch.cuda.device(d.device):
         check(_lib.lib().vkn_bits_mask_overlap(opt(d), opt(g), K, G, H, W, opt(inter), opt(area_dt), opt(area_gt), opt(ws), need, _stream()))
     return inter, area_dt, area_gt
+
+
+# ------------------------------------------------------------------------------------------- Swin backbone
+_SWIN = _lib.SWIN
+
+
+def swin_window_attention_supported(B, H, W, heads, window, shift, head_dim=_SWIN['VKN_SWIN_HEAD_DIM']):
+    """The envelope of `swin_window_attention` (include/vkn_swin.h), sizes included.  Asks the device nothing."""
+    return int(head_dim) == _SWIN['VKN_SWIN_HEAD_DIM'] and bool(
+        _lib.lib().vkn_swin_window_attn_supported(int(B), int(H), int(W), int(heads), int(window), int(shift)))
+
+
+def swin_window_attention(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale):
+    """The (shifted-)window attention of one Swin block (include/vkn_swin.h: vkn_swin_window_attn_f32).  qkv [B, H W, 3 heads 32] (or
+    [B, H, W, ...]): the rows of `attn.qkv(norm1(x))` on the tokens as they are; qkv_bias [3 heads 32] or None; bias_table
+    [(2 window - 1)^2, heads].  -> [B, H W, heads 32], what `attn.proj` takes.  One launch."""
+    qkv, bias_table = _req(qkv, 'qkv'), _req(bias_table, 'bias_table')
+    H, W, heads, window, shift = int(H), int(W), int(heads), int(window), int(shift)
+    C = heads * _SWIN['VKN_SWIN_HEAD_DIM']
+    B, D = (int(qkv.shape[0]) if qkv.dim() else 0), _SWIN['VKN_SWIN_HEAD_DIM']
+    if B < 1 or tuple(qkv.shape) not in ((B, H * W, 3 * C), (B, H, W, 3 * C), (B, H * W, 3, heads, D), (B, H, W, 3, heads, D)):
+        raise ValueError(f'swin_window_attention: qkv {tuple(qkv.shape)} is neither [B, {H * W}, {3 * C}] nor [B, {H}, {W}, 3, {heads}, {D}]')
+    if tuple(bias_table.shape) != ((2 * window - 1) ** 2, heads) or bias_table.device != qkv.device:
+        raise ValueError(f'swin_window_attention: bias_table {tuple(bias_table.shape)} is not [{(2 * window - 1) ** 2}, {heads}] on the device of qkv')
+    if qkv_bias is not None:
+        qkv_bias = _req(qkv_bias, 'qkv_bias')
+        if qkv_bias.numel() != 3 * C or qkv_bias.device != qkv.device:
+            raise ValueError(f'swin_window_attention: qkv_bias {tuple(qkv_bias.shape)} is not [{3 * C}] on the device of qkv')
+    out = torch.empty((B, H * W, C), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        check(_lib.lib().vkn_swin_window_attn_f32(_ptr(qkv), _ptr(qkv_bias), _ptr(bias_table), _ptr(out), B, H, W, heads, window, shift,
+                                                  float(scale), _stream()))
+    return out

@@ -97,6 +97,15 @@ except Exception:  # noqa: BLE001  (mmcv/mmdet are not installed in the build im
             self.init_assigner_sampler()
 
 
+try:  # mmdet's own table of backbones (`MODELS` in 2.18), where it has one: the Swin configs build `type='SwinTransformerDIY'` from it
+    from mmdet.models.builder import BACKBONES, build_backbone  # type: ignore
+except Exception:  # noqa: BLE001
+    BACKBONES = Registry('backbone')
+
+    def build_backbone(cfg):
+        return BACKBONES.build(cfg)
+
+
 def _register_training_components():
     """Losses / assigner / sampler of the training path.  Bundled registries: all of ours.  With mmdet present: OUR assigners and
     sampler replace the reference's in mmdet's own `BBOX_ASSIGNERS` / `BBOX_SAMPLERS` (force=True — our heads call
@@ -136,6 +145,10 @@ def register_head(cls):
 
 def register_neck(cls):
     return NECKS.register_module(force=True)(cls)
+
+
+def register_backbone(cls):
+    return BACKBONES.register_module(force=True)(cls)
 
 
 def register_transformer_layer(cls):
