@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libvkn.so')
-SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_wimage.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_segloss.hip', 'vkn_stq.hip', 'vkn_vpq.hip', 'vkn_fpn_bwd.hip', 'vkn_msda.hip', 'vkn_msda_bwd.hip', 'vkn_rle.hip', 'vkn_maskap.hip', 'vkn_instmask.hip', 'vkn_swin.hip', 'vkn_api.hip')
+SOURCES = ('vkn_gather.hip', 'vkn_update.hip', 'vkn_decode.hip', 'vkn_fused.hip', 'vkn_init.hip', 'vkn_panoptic.hip', 'vkn_merge.hip', 'vkn_assign.hip', 'vkn_assign_lr.hip', 'vkn_tracker.hip', 'vkn_loss.hip', 'vkn_chain.hip', 'vkn_chain_h2.hip', 'vkn_ksplit.hip', 'vkn_train.hip', 'vkn_wimage.hip', 'vkn_fpn.hip', 'vkn_optim.hip', 'vkn_tracktail.hip', 'vkn_trackloss.hip', 'vkn_gtprep.hip', 'vkn_segloss.hip', 'vkn_stq.hip', 'vkn_vpq.hip', 'vkn_fpn_bwd.hip', 'vkn_msda.hip', 'vkn_msda_bwd.hip', 'vkn_rle.hip', 'vkn_maskap.hip', 'vkn_instmask.hip', 'vkn_swin.hip', 'vkn_swin_bwd.hip', 'vkn_api.hip')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 # The C ABI, one header per part, each behind the headers it #includes.  A new part is one more name here.
 ABI_HEADERS = ('vkn.h', 'vkn_track.h', 'vkn_track_train.h', 'vkn_gt.h', 'vkn_decode.h')
@@ -46,6 +46,9 @@ INSTANCE_RESULT_HEADERS = ('vkn_instmask.h',)
 # Backbone parts: an eleventh such table `ABI_BACKBONE` behind the ten, on the same terms; its constants in their own record `SWIN`.
 # `_all_parts` stays the ten tables before it: the loops that bind go over `_all_tables`, the ten and this one.
 BACKBONE_HEADERS = ('vkn_swin.h',)
+# Backbone training parts: a twelfth such table `ABI_BACKBONE_TRAIN` behind the eleven, on the same terms; its constants in their own record
+# `WATTN_TRAIN`.  `_all_tables` stays the eleven tables before it: the loops that bind go over `_all_abi`, the eleven and this one.
+BACKBONE_TRAIN_HEADERS = ('vkn_wattn_train.h',)
 
 
 class VknLibraryError(RuntimeError):
@@ -175,11 +178,16 @@ def _all_parts(field):
 
 
 def _all_tables(field):
-    """`_all_parts`'s ten tables, then `ABI_BACKBONE`: every table that is bound"""
+    """`_all_parts`'s ten tables, then `ABI_BACKBONE`: the eleven tables before `ABI_BACKBONE_TRAIN`"""
     return _all_parts(field) + _each(field, (ABI_BACKBONE,))
 
 
-_EVERY_HEADER = ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS + TRAIN_HEADERS + NECK_HEADERS + NECK_TRAIN_HEADERS + RESULT_HEADERS + INSTANCE_METRIC_HEADERS + INSTANCE_RESULT_HEADERS + BACKBONE_HEADERS
+def _all_abi(field):
+    """`_all_tables`'s eleven tables, then `ABI_BACKBONE_TRAIN`: every table that is bound"""
+    return _all_tables(field) + _each(field, (ABI_BACKBONE_TRAIN,))
+
+
+_EVERY_HEADER = ABI_HEADERS + EXTENSION_HEADERS + METRIC_HEADERS + WINDOW_METRIC_HEADERS + TRAIN_HEADERS + NECK_HEADERS + NECK_TRAIN_HEADERS + RESULT_HEADERS + INSTANCE_METRIC_HEADERS + INSTANCE_RESULT_HEADERS + BACKBONE_HEADERS + BACKBONE_TRAIN_HEADERS
 _ALL = read_abi(INCLUDE, _EVERY_HEADER)          # ONE reading: includes resolve, a name declared twice is an error
 ABI = {h: _ALL[h] for h in ABI_HEADERS}
 ABI_EXT = {h: _ALL[h] for h in EXTENSION_HEADERS}
@@ -192,6 +200,7 @@ ABI_RESULT = {h: _ALL[h] for h in RESULT_HEADERS}
 ABI_INSTANCE_METRIC = {h: _ALL[h] for h in INSTANCE_METRIC_HEADERS}
 ABI_INSTANCE_RESULT = {h: _ALL[h] for h in INSTANCE_RESULT_HEADERS}
 ABI_BACKBONE = {h: _ALL[h] for h in BACKBONE_HEADERS}
+ABI_BACKBONE_TRAIN = {h: _ALL[h] for h in BACKBONE_TRAIN_HEADERS}
 HEADER, PROTOS, SYMBOLS, STRUCTS, MIRRORS = (getattr(ABI['vkn.h'], k) for k in ('path', 'protos', 'symbols', 'structs', 'mirrors'))
 CONSTS = {k: v for _, k, v in _each('consts', (ABI,))}      # every ABI header's constants: no name is declared twice
 SEG = ABI_EXT['vkn_seg_loss.h'].consts              # an extension's constants stay in its own record
@@ -204,6 +213,7 @@ RLE = ABI_RESULT['vkn_rle.h'].consts                # ... and a result part's
 MASKAP = ABI_INSTANCE_METRIC['vkn_maskap.h'].consts   # ... and an instance metric part's
 INSTMASK = ABI_INSTANCE_RESULT['vkn_instmask.h'].consts   # ... and an instance result part's
 SWIN = ABI_BACKBONE['vkn_swin.h'].consts                  # ... and a backbone part's
+WATTN_TRAIN = ABI_BACKBONE_TRAIN['vkn_wattn_train.h'].consts      # ... and a backbone training part's
 GT_MAX_IMAGES = CONSTS['VKN_GT_MAX_IMAGES']
 GT_MAX_CLASSES = CONSTS['VKN_GT_MAX_CLASSES']
 GT_MAX_IDS = CONSTS['VKN_GT_MAX_IDS']
@@ -230,7 +240,7 @@ def _ctype(base, depth, where, result=False):
     return ctypes.c_void_p
 
 
-for _h, _name, _fields in _all_tables('structs'):
+for _h, _name, _fields in _all_abi('structs'):
     _at = f'include/{_h}: {_name}'
     _ALL[_h].mirrors[_name] = _MIRROR[_name] = type(_name, (ctypes.Structure,), {
         '__doc__': f'Mirror of {_at} (device pointers as integers).',
@@ -251,7 +261,7 @@ POINTER_EXCEPTIONS = {
     ('vkn_msda_bwd_workspace_bytes', 'shapes'): ctypes.POINTER(ctypes.c_int),       # likewise
     ('vkn_msda_sample_bwd_f32', 'shapes'): ctypes.POINTER(ctypes.c_int),            # likewise
 }
-for _fn, _p in set(POINTER_EXCEPTIONS) - {(fn, q[0]) for _, fn, (_, params) in _all_tables('protos') for q in params}:
+for _fn, _p in set(POINTER_EXCEPTIONS) - {(fn, q[0]) for _, fn, (_, params) in _all_abi('protos') for q in params}:
     raise VknLibraryError(f'POINTER_EXCEPTIONS names {_fn}({_p}), which none of the headers {_EVERY_HEADER} declares')
 
 DEBUG_LIBPATH = os.path.join(LIBDIR, 'libvkn_debug.so')
@@ -346,12 +356,12 @@ def lib():
         raise VknLibraryError(f'{path} is missing — run `python -c "import __graft_entry__ as g; g.build()"` '
                               '(there is deliberately no CPU fallback)')
     L = ctypes.CDLL(path)
-    for h, name, (result, params) in _all_tables('protos'):
+    for h, name, (result, params) in _all_abi('protos'):
         fn, at = getattr(L, name), f'include/{h}: {name}'
         fn.restype = _ctype(*result, at, result=True)
         fn.argtypes = [POINTER_EXCEPTIONS.get((name, p)) or _ctype(base, depth, at) for p, base, depth in params]
     # header vs binary: structs are handed to the kernels verbatim, so a library built from another header means garbage pointers
-    for h, name, mirror in _all_tables('mirrors'):
+    for h, name, mirror in _all_abi('mirrors'):
         probe = 'vkn_sizeof_' + re.sub(r'(?<!^)(?=[A-Z])', '_', name[3:]).lower()
         if not any(probe in hdr.protos for hdr in _ALL.values()):        # any header may declare a struct's size probe
             raise VknLibraryError(f'include/{h} declares struct {name} without its size probe {probe}()')

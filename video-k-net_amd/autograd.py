@@ -484,3 +484,32 @@ def msda_sample(value, spatial_shapes, offsets, logits, ref, num_heads, num_poin
     `attention_weights` Linears (column ranges of one GEMM output are taken as they are); ref [Q, L, 2] -> [B, Q, M D], differentiable
     in value, offsets and logits."""
     return MSDASampleFn.apply(value, offsets, logits, ref, spatial_shapes, num_heads, num_points)
+
+
+class SwinWindowAttnFn(torch.autograd.Function):
+    """The (shifted-)window attention core of a Swin block, forward (`vkn_swin_window_attn_f32`, include/vkn_swin.h) and backward
+    (`vkn_wattn_bwd_f32`, include/vkn_wattn_train.h) on the library's kernels.  Only the operands are saved: the backward recomputes
+    scores and softmax, so no [B nW, heads, N, N] tensor outlives the forward.  No float atomics: two backward passes give the same bits.
+    The gradient of `qkv_bias` is the part through pad tokens only; the part through real tokens reaches the bias through `qkv`."""
+
+    @staticmethod
+    def forward(ctx, qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale):
+        qkv = qkv.contiguous()
+        ctx.save_for_backward(qkv, qkv_bias, bias_table)
+        ctx.cfg = (int(H), int(W), int(heads), int(window), int(shift), float(scale))
+        return ops.swin_window_attention(qkv, qkv_bias, bias_table, *ctx.cfg)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        qkv, qkv_bias, bias_table = ctx.saved_tensors
+        dqkv, dbias, dtable = ops.swin_window_attention_bwd(qkv, qkv_bias, bias_table, dout.contiguous(), *ctx.cfg)
+        need = ctx.needs_input_grad
+        return (dqkv if need[0] else None, dbias if qkv_bias is not None and need[1] else None, dtable if need[2] else None,
+                None, None, None, None, None, None)
+
+
+def swin_window_attention(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale):
+    """qkv [B, H W, 3 heads 32], the rows of the `qkv` Linear on the tokens as they lie; qkv_bias [3 heads 32] or None; bias_table
+    [(2 window - 1)^2, heads] -> [B, H W, heads 32], differentiable in all three."""
+    return SwinWindowAttnFn.apply(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale)

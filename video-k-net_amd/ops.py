@@ -2122,3 +2122,45 @@ def swin_window_attention(qkv, qkv_bias, bias_table, H, W, heads, window, shift,
         check(_lib.lib().vkn_swin_window_attn_f32(_ptr(qkv), _ptr(qkv_bias), _ptr(bias_table), _ptr(out), B, H, W, heads, window, shift,
                                                   float(scale), _stream()))
     return out
+
+
+def swin_window_attention_bwd_supported(B, H, W, heads, window, shift, head_dim=_SWIN['VKN_SWIN_HEAD_DIM']):
+    """The envelope of `swin_window_attention_bwd` (include/vkn_wattn_train.h): the forward's and a workspace below 2^31 bytes.  Asks the
+    device nothing."""
+    return int(head_dim) == _SWIN['VKN_SWIN_HEAD_DIM'] and bool(
+        _lib.lib().vkn_wattn_bwd_supported(int(B), int(H), int(W), int(heads), int(window), int(shift)))
+
+
+def swin_window_attention_bwd(qkv, qkv_bias, bias_table, dout, H, W, heads, window, shift, scale):
+    """The backward of `swin_window_attention` (include/vkn_wattn_train.h: vkn_wattn_bwd_f32) from its own operands and the gradient
+    dout [B, H W, heads 32] of its output -> (dqkv in the shape of qkv, dqkv_bias [3 heads 32] or None, dbias_table in the shape of
+    bias_table).  Nothing of the forward is needed: scores and softmax are recomputed.  `dqkv_bias` is ONLY the part of the bias gradient
+    that flows through pad tokens (their k and v are the bias); the part through real tokens follows from dqkv in the `qkv` Linear.  No
+    float atomics: two calls give the same bits.  Two launches."""
+    qkv, bias_table, dout = _req(qkv, 'qkv'), _req(bias_table, 'bias_table'), _req(dout, 'dout')
+    H, W, heads, window, shift = int(H), int(W), int(heads), int(window), int(shift)
+    D = _SWIN['VKN_SWIN_HEAD_DIM']
+    C = heads * D
+    B = int(qkv.shape[0]) if qkv.dim() else 0
+    if B < 1 or tuple(qkv.shape) not in ((B, H * W, 3 * C), (B, H, W, 3 * C), (B, H * W, 3, heads, D), (B, H, W, 3, heads, D)):
+        raise ValueError(f'swin_window_attention_bwd: qkv {tuple(qkv.shape)} is neither [B, {H * W}, {3 * C}] nor [B, {H}, {W}, 3, {heads}, {D}]')
+    if tuple(dout.shape) not in ((B, H * W, C), (B, H, W, C)) or dout.device != qkv.device:
+        raise ValueError(f'swin_window_attention_bwd: dout {tuple(dout.shape)} is not [{B}, {H * W}, {C}] on the device of qkv')
+    if tuple(bias_table.shape) != ((2 * window - 1) ** 2, heads) or bias_table.device != qkv.device:
+        raise ValueError(f'swin_window_attention_bwd: bias_table {tuple(bias_table.shape)} is not [{(2 * window - 1) ** 2}, {heads}] on the device of qkv')
+    if qkv_bias is not None:
+        qkv_bias = _req(qkv_bias, 'qkv_bias')
+        if qkv_bias.numel() != 3 * C or qkv_bias.device != qkv.device:
+            raise ValueError(f'swin_window_attention_bwd: qkv_bias {tuple(qkv_bias.shape)} is not [{3 * C}] on the device of qkv')
+    L_ = _lib.lib()
+    nb = L_.vkn_wattn_bwd_workspace_bytes(B, H, W, heads, window)
+    if not nb or not L_.vkn_wattn_bwd_supported(B, H, W, heads, window, shift):
+        raise ValueError(f'swin_window_attention_bwd: B {B}, map {H} x {W}, {heads} heads, window {window}, shift {shift} is outside the envelope')
+    dqkv = torch.empty_like(qkv)
+    dqkv_bias = torch.empty_like(qkv_bias) if qkv_bias is not None else None
+    dtable = torch.empty_like(bias_table)
+    ws = _workspace(nb, qkv.device, scratch=True)
+    with torch.cuda.device(qkv.device):
+        check(L_.vkn_wattn_bwd_f32(_ptr(qkv), _ptr(qkv_bias), _ptr(bias_table), _ptr(dout), _ptr(dqkv), _ptr(dqkv_bias), _ptr(dtable), B, H, W,
+                                   heads, window, shift, float(scale), _ptr(ws), ws.numel(), _stream()))
+    return dqkv, dqkv_bias, dtable

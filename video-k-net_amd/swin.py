@@ -5,7 +5,9 @@ Constructor keywords, defaults, state-dict keys (the persistent buffer `attn.rel
 `train()`, `init_weights(None)` and the output tuple are the reference's.  What differs is inside `SwinTransformerBlock.forward`: under
 the conditions of `fused_path` the pad, the two rolls, the window partition and its reverse, the `qkv` permute, the bias gather, the mask
 add, the softmax and the crop are `ops.swin_window_attention` on the rows of `attn.qkv(norm1(x))` as they lie.  Everywhere else
-`forward_torch` runs, the reference's composition op for op: it is what trains (there is no backward kernel) and what runs on the CPU.
+`forward_torch` runs, the reference's composition op for op: it is what trains by default and what runs on the CPU.  With `fused='train'`
+a block that needs a gradient keeps the kernel and differentiates it through `autograd.swin_window_attention`, whose backward is a second
+HIP kernel (include/vkn_wattn_train.h) that recomputes the softmax instead of saving it.
 
 The Linears, LayerNorms, the GELU MLP, `PatchEmbed` and `PatchMerging` are torch modules.  `timm` is not needed: `DropPath`, `to_2tuple`
 and `trunc_normal_` are the few lines below.  Loading a published Swin checkpoint `strict=True` is the decisive check of the key names.
@@ -16,7 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.utils.checkpoint as checkpoint
 
-from . import ops
+from . import autograd, ops
 from .registry import register_backbone
 
 trunc_normal_ = nn.init.trunc_normal_
@@ -114,6 +116,10 @@ class SwinTransformerBlock(nn.Module):
         super().__init__()
         self.dim, self.num_heads, self.window_size, self.shift_size, self.mlp_ratio = dim, num_heads, window_size, shift_size, mlp_ratio
         assert 0 <= self.shift_size < self.window_size, 'shift_size must in 0-window_size'
+        # fused: None = FUSED_DEFAULT, True / False, or 'train' = True and, where a gradient is needed, the kernel with its HIP backward
+        self.fused_backward = isinstance(fused, str) and fused == 'train'
+        if isinstance(fused, str) and not self.fused_backward:
+            raise ValueError(f"fused must be None, True, False or 'train', not {fused!r}")
         self.fused = FUSED_DEFAULT if fused is None else bool(fused)
         self.norm1 = norm_layer(dim)
         self.attn = WindowAttention(dim, window_size=to_2tuple(window_size), num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale,
@@ -122,14 +128,17 @@ class SwinTransformerBlock(nn.Module):
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
         self.H = self.W = None
-        self.last_path = None                      # 'fused' or 'torch': what the last forward took
+        self.last_path = None                      # 'fused', 'fused_train' or 'torch': what the last forward took
 
-    def fused_path(self, x):
+    def needs_grad(self, x):
+        return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.attn.parameters()) or self.norm1.weight.requires_grad)
+
+    def fused_path(self, x, train=False):
         """Whether this call may run the HIP kernel: the flag, CUDA fp32, nothing to differentiate, no attention dropout at work, and
-        the shape inside the envelope of include/vkn_swin.h."""
+        the shape inside the envelope of include/vkn_swin.h.  `train`: the same question with a gradient allowed."""
         if not (self.fused and x.is_cuda and x.dtype == torch.float32) or torch.is_autocast_enabled():      # (autocast: the Linears hand out fp16)
             return False
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.attn.parameters()) or self.norm1.weight.requires_grad):
+        if not train and self.needs_grad(x):
             return False
         if self.training and self.attn.attn_drop.p > 0:
             return False
@@ -138,11 +147,20 @@ class SwinTransformerBlock(nn.Module):
         return ops.swin_window_attention_supported(x.shape[0], self.H, self.W, self.num_heads, self.window_size, self.shift_size,
                                                    head_dim=self.dim // self.num_heads)
 
-    def attention_fused(self, x):
-        """norm1's output [B, H W, C] -> the attention branch before the residual: qkv Linear, the kernel, proj"""
+    def fused_train_path(self, x):
+        """Whether this call runs the kernel WITH its HIP backward: `fused='train'`, a gradient is needed (that alone turned `fused_path`
+        down), and the backward's envelope (include/vkn_wattn_train.h) holds the shape."""
+        if not (self.fused_backward and self.needs_grad(x) and self.fused_path(x, train=True)):
+            return False
+        return ops.swin_window_attention_bwd_supported(x.shape[0], self.H, self.W, self.num_heads, self.window_size, self.shift_size,
+                                                       head_dim=self.dim // self.num_heads)
+
+    def attention_fused(self, x, train=False):
+        """norm1's output [B, H W, C] -> the attention branch before the residual: qkv Linear, the kernel, proj.  `train`: the kernel
+        as an autograd function; the Linears stay torch autograd."""
         a = self.attn
-        y = ops.swin_window_attention(a.qkv(x), a.qkv.bias, a.relative_position_bias_table, self.H, self.W, self.num_heads,
-                                      self.window_size, self.shift_size, a.scale)
+        core = autograd.swin_window_attention if train else ops.swin_window_attention
+        y = core(a.qkv(x), a.qkv.bias, a.relative_position_bias_table, self.H, self.W, self.num_heads, self.window_size, self.shift_size, a.scale)
         return a.proj_drop(a.proj(y))
 
     def attention_torch(self, x, mask_matrix):
@@ -173,11 +191,14 @@ class SwinTransformerBlock(nn.Module):
         return x + self.drop_path(self.mlp(self.norm2(x)))
 
     def forward(self, x, mask_matrix):
+        train = False
         if not self.fused_path(x):
-            return self.forward_torch(x, mask_matrix)
+            train = self.fused_train_path(x)
+            if not train:
+                return self.forward_torch(x, mask_matrix)
         assert x.shape[1] == self.H * self.W, 'input feature has wrong size'
-        self.last_path = 'fused'
-        x = x + self.drop_path(self.attention_fused(self.norm1(x)))
+        self.last_path = 'fused_train' if train else 'fused'
+        x = x + self.drop_path(self.attention_fused(self.norm1(x), train))
         return x + self.drop_path(self.mlp(self.norm2(x)))
 
 
@@ -232,7 +253,7 @@ class BasicLayer(nn.Module):
         # block that takes the composition on the `x` that reaches IT — a block's output may need a gradient where the layer's input did not
         attn_mask = None
         for blk in self.blocks:
-            if attn_mask is None and blk.shift_size > 0 and not blk.fused_path(x):
+            if attn_mask is None and blk.shift_size > 0 and not blk.fused_path(x) and not blk.fused_train_path(x):
                 attn_mask = shift_attention_mask(H, W, self.window_size, self.shift_size, x.device, x.dtype)
             x = checkpoint.checkpoint(blk, x, attn_mask, use_reentrant=False) if self.with_cp else blk(x, attn_mask)
         if self.downsample is not None:
@@ -263,7 +284,8 @@ class PatchEmbed(nn.Module):
 
 @register_backbone
 class SwinTransformerDIY(nn.Module):
-    """The reference's keywords and defaults; `fused` (None = `FUSED_DEFAULT`) is this package's one addition."""
+    """The reference's keywords and defaults; `fused` (None = `FUSED_DEFAULT`, True, False, or 'train': the kernel also where a gradient
+    is needed, with its HIP backward) is this package's one addition."""
 
     def __init__(self, pretrain_img_size=224, patch_size=4, in_chans=3, embed_dims=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24],
                  window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.2,
